@@ -18,9 +18,16 @@ live on their gene's rank, Inheritance links on their handle's owner; And
 joins are placed by cost (co-located / broadcast / all-to-all exchange,
 das_amd/parallel.py); per-rank KB size is fixed (weak scaling).
 
-The default run (`--workload all`) then measures the other configurations
-one after another in the same process and adds their lines under
-"workloads" (each with its own roofline, kernel table and CPU baseline):
+A plain run sets up, warms up, times the steps and prints the line (its
+roofline from the events of the timed steps, its kernel table from the last
+warm-up step); `--dump-outputs DIR` adds the last timed step's answers as
+.npy files.  `--full` adds what takes runs of its own: CPU baselines, the
+step check against the other submission mode, per-query timings, join-probe
+variants, the materialisation-inclusive figure, the store-bandwidth probe,
+the detail file, and with `--workload all` (the default) the other
+configurations, measured one after another in the same process with their
+lines under "workloads" (each with its own roofline, kernel table and CPU
+baseline):
   flybase  config 3: FlyBase-shaped Execution(Schema, key, value) KB, the
            QueryFlyBase.ipynb And / And+Not / Or query shapes, a fresh gene
            anchor per step (fixed KB, links sharded by handle: strong scaling)
@@ -58,10 +65,19 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline's timed steps: the extra workloads of --workload all, CPU "
+                         "baselines, the step check against the other submission mode, per-query timings, join-probe "
+                         "variants, the materialisation-inclusive figure, the store-bandwidth probe and the detail "
+                         "file.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float64; "
+                         "query workloads): counts.npy, per query an order-independent checksum of its whole answer "
+                         "and a fixed seeded sample of its rows, sorted; index.json names the files")
     ap.add_argument("--workload", default="all", choices=["all", "bio", "flybase", "hub", "build", "load",
                                                           "getlinks"])
     ap.add_argument("--legs", default="auto",
-                    help="with --workload all: comma list of the extra workloads (auto: flybase,hub,build,getlinks "
+                    help="with --full --workload all: comma list of the extra workloads (auto: flybase,hub,build,getlinks "
                          "on one GPU; build at N > 1)")
     ap.add_argument("--leg-cpu-seconds", type=float, default=8.0,
                     help="CPU-baseline budget of each extra workload of --workload all")
@@ -107,10 +123,20 @@ def parse():
     ap.add_argument("--materialise-cap", type=int, default=2_000_000,
                     help="largest answer whose Python objects the materialisation-inclusive figure builds")
     ap.add_argument("--cprofile", default=None, help="write a host-side cProfile of 3 extra steps here")
-    ap.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
-                    help="file for the full record (kernel tables, join variants, materialisation); the last stdout "
-                         "line is the compact <= 4 KB summary")
-    return ap.parse_args()
+    ap.add_argument("--detail", default=None,
+                    help="file for the full record (kernel tables, join variants, materialisation; with --full: "
+                         "bench_out/bench_detail.json unless given); the last stdout line is the compact <= 4 KB "
+                         "summary")
+    args = ap.parse_args()
+    if args.dump_outputs and args.workload in ("build", "load", "getlinks"):
+        ap.error("--dump-outputs: query workloads only (all, bio, flybase, hub)")
+    if args.full:
+        if args.detail is None:
+            args.detail = os.path.join(ROOT, "bench_out", "bench_detail.json")
+    else:
+        # a plain run: the headline's set-up, warm-up and timed steps alone
+        args.no_cpu_baseline = args.no_materialise = args.no_extras = True
+    return args
 
 
 # ---------------------------------------------------------------------------
@@ -1055,6 +1081,106 @@ def verify_steps(batched, single, names, dist, stage):
                                                       "equal matched() one query at a time on the same query set"}
 
 
+# ---------------------------------------------------------------------------
+# --dump-outputs: the last timed step's answers as .npy files, comparable
+# between two builds (an answer is a set: nothing here depends on row order)
+# ---------------------------------------------------------------------------
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_ROWS = 1 << 16          # a larger table keeps 1 row in 2^s, s the least with rows / 2^s <= this
+_DUMP_SEED, _DUMP_MULT = 0x2545F4914F6CDD1D, -0x61C8864680B583EB      # (0x9E3779B97F4A7C15 as int64)
+
+
+def _var_salt(name):
+    """tests/checksum.py's per-variable key of das_table_checksum."""
+    import hashlib
+    return int.from_bytes(hashlib.md5(b"das-var:" + name.encode()).digest()[:8], "little")
+
+
+def _sample_rows(db, t, shift):
+    """Rows of the device table `t` as an (n, ncols) uint32 host array: all of
+    them (shift 0), or those whose seeded hash of the row's values has `shift`
+    zero bits -- a fixed sample whatever order the rows are stored in.  The
+    rows are copied and hashed on the device (das_table_export_rows + torch)."""
+    import numpy as np
+    import torch
+    n, k = int(t.nrows), len(t.vars)
+    dev = torch.device("cuda", db.ctx.device)
+    buf = torch.empty((n, k), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    db.ctx.export_rows(t, buf.data_ptr())
+    torch.cuda.synchronize()
+    if shift == 0:
+        return buf.cpu().numpy().view(np.uint32)
+    kept, chunk = [], 1 << 24
+    for lo in range(0, n, chunk):
+        part = buf[lo:lo + chunk]
+        h = torch.full((part.shape[0],), _DUMP_SEED, dtype=torch.int64, device=dev)
+        for c in range(k):
+            h = (h ^ (part[:, c].to(torch.int64) & 0xFFFFFFFF)) * _DUMP_MULT      # int64 arithmetic wraps
+            h = h ^ ((h >> 31) & 0x1FFFFFFFF)
+        kept.append(part[((h >> 20) & ((1 << shift) - 1)) == 0].cpu())
+    return torch.cat(kept).numpy().view(np.uint32)
+
+
+def dump_outputs(out_dir, db, pm, names, counts, answers):
+    """DIR/counts.npy: the answer size of each query of the last timed step
+    (what the step returns).  Per query q of a one-GPU run, from the answer
+    object the step's matched() / matched_many call produced:
+      q<q>_checksum.npy  das_table_checksum over all rows of its ordered
+                         tables (tests/checksum.py), as four 16-bit limbs,
+                         least significant first
+      q<q>_rows<g>.npy   its rows per variable set g: columns in variable-name
+                         order, every value the leading 48 bits of the bound
+                         atom's handle, rows sorted; all rows of a table of up
+                         to DUMP_SAMPLE_ROWS rows, else the seeded sample of
+                         _sample_rows
+    All float64 (exact for these integers), DUMP_MAX_BYTES at most in all;
+    index.json says what each file holds."""
+    import numpy as np
+    from das_amd import _lib
+    os.makedirs(out_dir, exist_ok=True)
+    index, left = {}, [DUMP_MAX_BYTES]
+
+    def save(name, arr, what):
+        arr = np.ascontiguousarray(arr, dtype=np.float64)
+        if arr.nbytes + 128 > left[0]:
+            log(f"dump: {name} left out ({arr.nbytes} bytes, over the {DUMP_MAX_BYTES}-byte bound)")
+            return
+        left[0] -= arr.nbytes + 128
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        index[name] = what
+
+    save("counts", counts, {"what": "answer size of each query of the last timed step", "queries": list(names)})
+    for q, ans in enumerate(answers or []):
+        total, groups = 0, {}
+        for t in db.rel_local_tables(ans._relation()):
+            if t.kind != _lib.TABLE_ORDERED or not t.nrows or not t.vars:
+                continue
+            vnames = [pm._var_name(v) for v in t.vars]
+            s, bad = t.checksum([_var_salt(v) for v in vnames])
+            if bad:
+                raise AssertionError(f"{names[q]}: {bad} answer values are not atom ids")
+            total = (total + s) & ((1 << 64) - 1)
+            order = sorted(range(len(vnames)), key=vnames.__getitem__)
+            groups.setdefault(tuple(vnames[i] for i in order), []).append((t, order))
+        save(f"q{q}_checksum", [(total >> (16 * i)) & 0xFFFF for i in range(4)],
+             {"query": names[q], "what": "das_table_checksum of the whole answer, 16-bit limbs, least significant first"})
+        for g, (cols, members) in enumerate(sorted(groups.items())):
+            n = sum(int(t.nrows) for t, _ in members)
+            shift = max(0, (n - 1).bit_length() - (DUMP_SAMPLE_ROWS.bit_length() - 1))
+            rows = np.concatenate([_sample_rows(db, t, shift)[:, order] for t, order in members])
+            ids, inv = np.unique(rows, return_inverse=True)
+            vals = np.array([int(h[:12], 16) for h in db.hex_of(ids)], dtype=np.float64)
+            rows = vals[inv].reshape(rows.shape)
+            rows = rows[np.lexsort(rows.T[::-1])][:2 * DUMP_SAMPLE_ROWS]
+            save(f"q{q}_rows{g}", rows,
+                 {"query": names[q], "columns": list(cols), "answer_rows": n, "kept": int(rows.shape[0]),
+                  "sample": "every row" if shift == 0 else f"1 row in {1 << shift} by a seeded hash of the row",
+                  "values": "leading 48 bits of each atom's handle; rows sorted"})
+    with open(os.path.join(out_dir, "index.json"), "w") as f:
+        json.dump(index, f, indent=1)
+
+
 def run_query(args, workload, rank, world, dist, local_rank, backend):
     """One query workload (bio / flybase / hub): KB, warmup, K timed steps
     between barriers, max over ranks.  Returns rank 0's JSON dict."""
@@ -1098,9 +1224,11 @@ def run_query(args, workload, rank, world, dist, local_rank, backend):
         def run(q):
             return engine.count(q)
     else:
-        def run(q):
+        def run(q, keep=None):
             ans = pm.PatternMatchingAnswer()
             q.matched(db, ans)
+            if keep is not None:
+                keep.append(ans)
             return ans.count()
 
     # Q2's launches are tagged inside the timed steps (das_prof_tag_plan:
@@ -1110,8 +1238,9 @@ def run_query(args, workload, rank, world, dist, local_rank, backend):
     # instantiation.  The step is the same batch with or without the tag.
     tag_q2 = [False]
 
-    def step(i, batch=None):
-        """One pass over query set i -> the answer size of each query."""
+    def step(i, batch=None, keep=None):
+        """One pass over query set i -> the answer size of each query
+        (keep: a list that receives the step's answer objects, one GPU)."""
         if engine is not None:
             if batch is False:
                 return [run(q) for _, q in qsets[i]]
@@ -1123,13 +1252,15 @@ def run_query(args, workload, rank, world, dist, local_rank, backend):
             # the step's queries in one das_plan_execute_many call
             # (pm.matched_many: a fused chain's GPU time overlaps the host
             # work of the next query)
-            return [a.count() for _, a in pm.matched_many(db, [q for _, q in qsets[i]],
-                                                           tag=None if q2 is None else (q2, "Q2"))]
+            res = pm.matched_many(db, [q for _, q in qsets[i]], tag=None if q2 is None else (q2, "Q2"))
+            if keep is not None:
+                keep.extend(a for _, a in res)
+            return [a.count() for _, a in res]
         out = []
         for k, (name, q) in enumerate(qsets[i]):
             if k == q2:
                 db.ctx.prof_tag("Q2")
-            out.append(run(q))
+            out.append(run(q) if keep is None else run(q, keep))
             if k == q2:
                 db.ctx.prof_tag(None)
         return out
@@ -1155,8 +1286,9 @@ def run_query(args, workload, rank, world, dist, local_rank, backend):
     db.ctx.prof_enable(False)
     warm_stats = db.ctx.prof_stats()
     dominant = roofline_of(warm_stats, workload) if args.events == "dominant" else None
-    per_query = {name: run(q) for name, q in qsets[args.warmup]}          # one by one: matched() per query
-    if world > 1:
+    # one by one: matched() per query (a plain run takes the sizes from its first timed step)
+    per_query = {name: run(q) for name, q in qsets[args.warmup]} if args.full else None
+    if world > 1 and per_query is not None:
         # the answer's size: each rank counts the bindings it holds
         stage = torch.device("cuda", local_rank) if backend == "nccl" else "cpu"
         per_query = dict(zip(per_query, (int(x) for x in _sync_sum(dist, list(per_query.values()), stage))))
@@ -1209,8 +1341,10 @@ def run_query(args, workload, rank, world, dist, local_rank, backend):
     t0 = time.perf_counter()
     log("timed steps")
     step_counts = []
+    # --dump-outputs: the last timed step's answer objects are kept for the dump
+    last_answers = [] if args.dump_outputs and engine is None else None
     for i in range(args.steps):
-        step_counts.append(step(args.warmup + i))
+        step_counts.append(step(args.warmup + i, keep=last_answers if i == args.steps - 1 else None))
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
@@ -1232,9 +1366,23 @@ def run_query(args, workload, rank, world, dist, local_rank, backend):
     # time, one-by-one steps against one das_plan_execute_many batch -- the
     # per-query answer sizes and so the step's total must be equal
     other = not args.batch
-    check = verify_steps(step_counts, [step(args.warmup + i, batch=other) for i in range(args.steps)],
-                         [[name for name, _ in qsets[args.warmup + i]] for i in range(args.steps)], dist, stage_dev)
-    check["against"] = "pm.matched_many batches" if other else "matched() one query at a time"
+    if per_query is None and args.steps:
+        per_query = dict(zip((name for name, _ in qsets[args.warmup]),
+                             (int(x) for x in _sync_sum(dist, step_counts[0], stage_dev))))
+    if args.dump_outputs and args.steps:
+        last = [int(x) for x in _sync_sum(dist, step_counts[-1], stage_dev)]
+        if rank == 0:
+            log(f"writing the last timed step's outputs to {args.dump_outputs}")
+            dump_outputs(args.dump_outputs, db, pm, [name for name, _ in qsets[args.warmup + args.steps - 1]], last,
+                         last_answers)
+        last_answers = None
+        torch.cuda.empty_cache()
+    check = None
+    if args.full:
+        check = verify_steps(step_counts, [step(args.warmup + i, batch=other) for i in range(args.steps)],
+                             [[name for name, _ in qsets[args.warmup + i]] for i in range(args.steps)], dist,
+                             stage_dev)
+        check["against"] = "pm.matched_many batches" if other else "matched() one query at a time"
     # the other submission mode, timed over query sets no earlier step used:
     # matched() per query is the reference's call pattern
     # (scripts/benchmark.py:231-239, QueryFlyBase.ipynb cells 5-9)
@@ -1535,7 +1683,7 @@ def main():
         head = "bio"
         legs = args.legs.split(",") if args.legs != "auto" else (["flybase", "hub", "build", "getlinks"]
                                                                  if world == 1 else ["build"])
-        legs = [w for w in legs if w]
+        legs = [w for w in legs if w] if args.full else []
     else:
         head, legs = args.workload, []
 
@@ -1560,7 +1708,7 @@ def main():
             _free_device()
             continue
         t_leg = time.perf_counter()
-        a = argparse.Namespace(**dict(vars(args), cpu_baseline_seconds=args.leg_cpu_seconds))
+        a = argparse.Namespace(**dict(vars(args), cpu_baseline_seconds=args.leg_cpu_seconds, dump_outputs=None))
         if w == "flybase":
             # a latency-bound step of ~0.25 ms: more untimed warmup steps (the
             # side streams' blocks, pinned pools, shape caches) and more timed
@@ -1579,12 +1727,13 @@ def main():
     # measured after the legs: write-bound fractions move with the card
     box = None
     try:
-        from das_amd.database.hip_db import HipDB
-        probe = HipDB(device=local_rank)
-        gbps = probe.ctx.box_store_bw(4 << 30, 5)
-        box = {"store16_nt_GBps": round(gbps, 1), "store16_nt_frac": round(gbps / HBM_PEAK_GBS, 4),
-               "how": "das_box_store_bw: 4 GiB as six columns of nontemporal dwordx4 stores, 5 launches"}
-        del probe
+        if args.full:
+            from das_amd.database.hip_db import HipDB
+            probe = HipDB(device=local_rank)
+            gbps = probe.ctx.box_store_bw(4 << 30, 5)
+            box = {"store16_nt_GBps": round(gbps, 1), "store16_nt_frac": round(gbps / HBM_PEAK_GBS, 4),
+                   "how": "das_box_store_bw: 4 GiB as six columns of nontemporal dwordx4 stores, 5 launches"}
+            del probe
     except Exception as e:                  # the line is still written
         box = {"error": f"{type(e).__name__}: {e}"[:200]}
     if rank == 0:

@@ -11,7 +11,7 @@ mkdir -p gpurun_out/$T
 OUT=gpurun_out/$T/ab_${W}_${AB_VAR}.jsonl
 : > $OUT
 for v in ${AB_A} ${AB_B} ${AB_A} ${AB_B}; do
-    env $AB_VAR=$v timeout -k 10 ${AB_TIMEOUT:-240} python bench.py --workload $W --steps ${STEPS:-10} \
+    env $AB_VAR=$v timeout -k 10 ${AB_TIMEOUT:-240} python bench.py --full --workload $W --steps ${STEPS:-10} \
         --warmup ${WARMUP:-3} --no-cpu-baseline --no-materialise ${BENCH_ARGS:-} \
         --detail gpurun_out/$T/ab_${W}_${AB_VAR}_$v.json > gpurun_out/$T/ab_line.json \
         2> gpurun_out/$T/ab_${W}.err || exit 1

@@ -2,7 +2,7 @@
 # One GPU session (run through gpurun from the repo root).  MODES picks the
 # steps, in order (default "tests profile"):
 #   tests    the GPU parity suite (TESTS selects files, K a -k expression; default all)
-#   bench    the default bench.py run exactly as the driver runs it
+#   bench    the bench.py --full run: the headline and every other workload
 #            (BENCH_ARGS adds flags) -> gpurun_out/$TAG/bench.json + detail
 #   profile  tools/profile_bench.sh for each workload in WORKLOADS (rocprof
 #            kernel trace + FETCH/WRITE PMC passes + roofline check)
@@ -19,7 +19,7 @@ run_tests() {
         --timeout-method thread --durations=15 > gpurun_out/$T/tests.txt 2>&1
 }
 run_bench() {
-    timeout -k 10 ${BENCH_TIMEOUT:-420} python bench.py --gpus 1 --steps ${STEPS:-20} --warmup ${WARMUP:-5} \
+    timeout -k 10 ${BENCH_TIMEOUT:-420} python bench.py --full --gpus 1 --steps ${STEPS:-20} --warmup ${WARMUP:-5} \
         --detail gpurun_out/$T/bench_detail.json ${BENCH_ARGS:-} > gpurun_out/$T/bench.json 2> gpurun_out/$T/bench.err
 }
 run_profiles() {

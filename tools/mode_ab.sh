@@ -11,7 +11,7 @@ for rep in $(seq 1 ${REPS:-2}); do
     extra=""
     case $m in *:none) extra="--events none" ;; esac
     out=gpurun_out/mode_${W}_b$(echo $m | tr ':' '_')_$rep
-    env $ENVS timeout -k 10 300 python bench.py --workload $W --batch $b --steps 20 --warmup 5 --no-cpu-baseline \
+    env $ENVS timeout -k 10 300 python bench.py --full --workload $W --batch $b --steps 20 --warmup 5 --no-cpu-baseline \
         --no-materialise $extra --detail $out.json > $out.out 2> $out.err
     echo "$W mode=$m rep $rep: $(tail -1 $out.out | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('timed', d['ms_per_step'], 'batched', d.get('step_ms_batched'), 'matched', d.get('step_ms_matched'), 'box', (d.get('box') or {}).get('store16_nt_GBps'))")"
   done

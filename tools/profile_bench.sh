@@ -20,7 +20,7 @@ T=${TAG:-r2}
 D=gpurun_out/prof_${T}_$W
 mkdir -p $D
 export TMPDIR=/tmp
-ARGS="--workload $W --steps ${STEPS:-10} --warmup ${WARMUP:-3} ${BENCH_ARGS:-}"
+ARGS="--full --workload $W --steps ${STEPS:-10} --warmup ${WARMUP:-3} ${BENCH_ARGS:-}"
 # which box: the card's serial / unique id and its clocks next to the records
 # (box-to-box spreads of the write-bound kernels are then attributable)
 { date -u; hostname; rocm-smi --showserial --showuniqueid --showclocks 2>&1 || true; } > gpurun_out/${T}_${W}_box.txt

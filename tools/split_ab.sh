@@ -12,7 +12,7 @@ k=0
 for cfg in $CFGS; do
   k=$((k + 1))
   tag=$(echo "$cfg" | tr '=,' '__')_$k
-  args="--workload $W --steps ${STEPS:-20} --warmup ${WARMUP:-5} --no-cpu-baseline --no-materialise --no-extras"
+  args="--full --workload $W --steps ${STEPS:-20} --warmup ${WARMUP:-5} --no-cpu-baseline --no-materialise --no-extras"
   envs=""
   if [ "$cfg" = "b0" ] || [ "$cfg" = "b1" ]; then args="$args --batch ${cfg#b}"; elif [ "$cfg" != "base" ]; then envs=$(echo "$cfg" | tr ',' ' '); fi
   D=gpurun_out/split_${W}_${SES:-s}/$tag
