@@ -69,6 +69,16 @@ class das_template_scan_t(C.Structure):
     ]
 
 
+class das_name_dfa_t(C.Structure):
+    _fields_ = [
+        ("n_states", C.c_uint32), ("n_classes", C.c_uint32), ("start", C.c_uint32), ("eot_class", C.c_uint32),
+        ("byte_class", C.c_uint8 * 256), ("next", C.c_void_p), ("accept", C.c_void_p),
+    ]
+
+
+NAME_STAGE_BYTES = 16384          # DAS_NAME_STAGE_BYTES: name bytes of one tile the matcher stages in LDS
+
+
 class das_plan_node_t(C.Structure):
     _fields_ = [
         ("op", C.c_int32), ("nchild", C.c_uint32), ("value", C.c_uint32), ("dedup", C.c_uint32),
@@ -109,6 +119,8 @@ _SIGS = {
     "das_link_targets": (C.c_int, [P, C.c_uint32, P, C.c_uint32, P]),
     "das_ctype_lookup": (C.c_int, [P, P, P]),
     "das_incoming": (C.c_int, [P, C.c_uint32, P, C.c_uint64, P]),
+    "das_match_node_names": (C.c_int, [P, C.c_uint32, P, P, C.c_uint64, P]),
+    "das_node_name_stats": (C.c_int, [P, C.c_uint32, P, P, P]),
     "das_export_outgoing": (C.c_int, [P, P, P, P, P]),
     "das_counters": (C.c_int, [P]),
     "das_scan_link": (C.c_int, [P, C.POINTER(das_link_scan_t), C.POINTER(P)]),
@@ -535,6 +547,32 @@ class Context:
         if n.value:
             check(lib().das_incoming(self.h, int(atom_id), ptr(out), n.value, C.byref(n)), self.h)
         return out[:n.value]
+
+    def node_name_stats(self, type_id):
+        """(nodes, name bytes, ascii_only) of one named type (das_node_name_stats)."""
+        n, b, a = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        check(lib().das_node_name_stats(self.h, int(type_id), C.byref(n), C.byref(b), C.byref(a)), self.h)
+        return n.value, b.value, bool(a.value)
+
+    def match_node_names(self, type_id, dfa, cap=None):
+        """Ids (ascending) of the nodes of a named type whose name the DFA
+        accepts (das_match_node_names; `dfa`: name_search.NameDFA or any
+        object with its fields).  cap: copy at most that many ids; the second
+        value is the number of matches."""
+        nxt = np.ascontiguousarray(dfa.next, dtype=np.uint16)
+        acc = np.ascontiguousarray(dfa.accept, dtype=np.uint8)
+        cls = np.ascontiguousarray(dfa.byte_class, dtype=np.uint8)
+        if cls.size != 256 or nxt.size < dfa.n_states * dfa.n_classes or acc.size < dfa.n_states:
+            raise ValueError("name DFA: table smaller than n_states / n_classes say")
+        d = das_name_dfa_t(n_states=dfa.n_states, n_classes=dfa.n_classes, start=dfa.start, eot_class=dfa.eot_class,
+                           next=ptr(nxt), accept=ptr(acc))
+        C.memmove(d.byte_class, cls.tobytes(), 256)
+        if cap is None:
+            cap = self.node_name_stats(type_id)[0]
+        out = np.empty(max(int(cap), 1), dtype=np.uint32)
+        n = C.c_uint64()
+        check(lib().das_match_node_names(self.h, int(type_id), C.byref(d), ptr(out), int(cap), C.byref(n)), self.h)
+        return out[:min(n.value, int(cap))], n.value
 
     def ctype_lookup(self, digest):
         d = np.ascontiguousarray(np.asarray(digest, dtype=np.uint32))

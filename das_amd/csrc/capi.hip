@@ -512,6 +512,27 @@ int das_incoming(das_ctx_t* ctx, uint32_t id, uint32_t* out, uint64_t cap, uint6
   });
 }
 
+int das_match_node_names(das_ctx_t* ctx, uint32_t type_id, const das_name_dfa_t* dfa, uint32_t* out_ids, uint64_t cap,
+                         uint64_t* n) {
+  return guarded(ctx, [&] {
+    DAS_CHECK(dfa && n, das::DAS_E_INVALID, "null argument");
+    *n = das::match_node_names(ctx->c, type_id, *dfa, out_ids, cap);
+  });
+}
+
+int das_node_name_stats(das_ctx_t* ctx, uint32_t type_id, uint64_t* n_nodes, uint64_t* n_bytes,
+                        uint32_t* ascii_only) {
+  return guarded(ctx, [&] {
+    DAS_CHECK(ctx->c.idx.built, das::DAS_E_NOT_BUILT, "index not built");
+    DAS_CHECK(type_id < ctx->c.idx.n_types, das::DAS_E_INVALID, "named type id out of range");
+    das::ensure_name_heap(ctx->c);
+    const das::NameHeap& h = ctx->c.idx.names;
+    if (n_nodes) *n_nodes = h.type_hi[type_id] - h.type_lo[type_id];
+    if (n_bytes) *n_bytes = h.type_bytes[type_id];
+    if (ascii_only) *ascii_only = h.type_ascii[type_id];
+  });
+}
+
 int das_ctype_lookup(das_ctx_t* ctx, const uint32_t digest[4], int64_t* ctype_id) {
   return guarded(ctx, [&] {
     const auto& v = ctx->c.idx.ctype_digest;

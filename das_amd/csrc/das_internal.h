@@ -79,6 +79,22 @@ struct CtypeRange {
   uint64_t begin, end;        // rows of ctab[arity]
 };
 
+// Resident node names (names.hip), built by the first name search after an
+// index build: the nodes in ascending id order, their name bytes back to
+// back, and -- ids being clustered by named type -- each type's range of
+// that list.  The device arrays are the index's (Index::owned).
+struct NameHeap {
+  bool built = false;
+  uint64_t n_nodes = 0, n_bytes = 0;
+  uint32_t* node_id = nullptr;   // [n_nodes] ids of the nodes, ascending
+  uint64_t* off = nullptr;       // [n_nodes + 1] byte offsets into `bytes`
+  uint8_t* bytes = nullptr;      // [n_bytes rounded up to 16, + 16] name bytes in node_id order
+  std::vector<uint64_t> type_lo, type_hi;   // host: nodes [lo, hi) of the list per named type
+  std::vector<uint64_t> type_bytes;         // host: name bytes per named type
+  std::vector<uint8_t> type_ascii;          // host: 1 = every name byte of the type is < 0x80 and not '\n'
+  uint64_t device_bytes = 0;
+};
+
 struct Index {
   bool built = false;
   hipStream_t stream = nullptr;  // stream the index arrays were allocated on (caching allocator)
@@ -121,6 +137,7 @@ struct Index {
   // nodes without a device round trip
   std::vector<Digest> h_node_dig;
   std::vector<uint32_t> h_node_id, h_node_type;
+  NameHeap names;                                              // built on demand (ensure_name_heap)
   std::vector<void*> owned;                                    // device allocations
   std::map<std::array<uint64_t, 4>, std::pair<uint64_t, uint64_t>> range_cache;   // P lookups
   uint64_t device_bytes = 0;
@@ -355,6 +372,15 @@ void lookup_digests(Ctx& c, const Digest* h_digests, uint64_t n, int64_t* h_ids)
 // trip (false: batch too large, use lookup_digests + das_atoms_info)
 bool lookup_small(Ctx& c, const Digest* h_digests, uint64_t n, int64_t* h_ids, uint8_t* cat, uint32_t* arity,
                   uint32_t* type);
+
+// names.hip: node-name search (das_match_node_names)
+void ensure_name_heap(Ctx& c);
+// throws DAS_E_INVALID unless `d` is inside the limits, every entry in range
+// and every accepting state absorbing (host checks only)
+void check_name_dfa(const das_name_dfa_t& d);
+// ids (ascending) of the nodes of `type_id` whose name `d` accepts: the
+// number of matches; min(that, cap) ids copied to the host array out_ids
+uint64_t match_node_names(Ctx& c, uint32_t type_id, const das_name_dfa_t& d, uint32_t* out_ids, uint64_t cap);
 
 // Column pointers of a table (kernel argument by value).
 struct ColSet {

@@ -1,0 +1,396 @@
+// Node-name search on the device (das_match_node_names, das_node_name_stats):
+// the resident name heap and the DFA matcher behind
+// HipDB.get_matched_node_name (redis_mongo_db.py:287-293).  DESIGN.md §3c.
+//
+// Heap: the nodes (cat == 1) in ascending id order, each node's name bytes
+// back to back, n_nodes + 1 byte offsets.  Ids are clustered by named type
+// (index.hip step 3b), so the nodes of one type are one range of that list.
+// Built on the first call after an index build -- a KB that never searches
+// names pays nothing -- from the context's host copy of the loader's leaf
+// strings; the name of a node is its "Type name" leaf without the type name
+// and the blank (AtomArrays.node_name: name_start == len(type name) + 1).
+//
+// Matcher: one lane per name, tiles of kNameBlock consecutive names.  The
+// automaton's table and the tile's heap bytes are staged in LDS; a lane walks
+// its name with one table lookup per byte and stops at the first accepting
+// state (accepting states are absorbing).  The kernel knows nothing about
+// regular expressions: das_name_dfa_t is the whole contract.
+#include <algorithm>
+#include <cstring>
+
+#include "das_internal.h"
+
+namespace das {
+namespace {
+
+constexpr unsigned kNameBlock = 256;                      // threads = names per tile
+constexpr uint32_t kNameStage = DAS_NAME_STAGE_BYTES;     // a tile's names up to this many bytes are walked from LDS
+// staged image: the tile's bytes from the 16-byte boundary at or below its
+// first byte (head: up to 15 bytes of the previous tile), in whole uint4s
+constexpr uint32_t kStageCap = kNameStage + 16;
+constexpr uint32_t kStageVecs = kStageCap / 16 + 1;       // + one: the word at offset kStageCap may be read, never used
+constexpr uint32_t kMaxTable = DAS_NAME_DFA_MAX_TABLE;
+constexpr uint32_t kAcceptBit = 0x8000u;                  // staged table entry: next state's row base | accept << 15
+static_assert(kMaxTable <= kAcceptBit, "a row base must fit below the accept bit");
+static_assert(2 * kMaxTable + 256 + 16 * kStageVecs <= 64 * 1024, "table + staging within 64 KiB of LDS");
+
+inline dim3 G(uint64_t n) { return dim3(grid_for(n, 256)); }
+
+template <typename T>
+T* dalloc(Index& idx, uint64_t count) {
+  if (!count) count = 1;
+  T* p = (T*)cache_alloc(sizeof(T) * count, idx.stream);
+  idx.owned.push_back(p);
+  idx.device_bytes += sizeof(T) * count;
+  return p;
+}
+
+struct NodeFlagIn {
+  const uint8_t* cat;
+  __device__ __forceinline__ uint32_t operator()(uint64_t i) const { return cat[i] == CAT_NODE ? 1u : 0u; }
+};
+
+// node_id[pos[i]] = i for every node i (ascending ids)
+__global__ void k_name_nodes(const uint8_t* cat, const uint32_t* pos, uint64_t n_atoms, uint32_t* node_id) {
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n_atoms; i += (uint64_t)gridDim.x * blockDim.x)
+    if (cat[i] == CAT_NODE) node_id[pos[i]] = (uint32_t)i;
+}
+
+// Where node j's name lies in the loader's leaf bytes.
+struct NameSrc {
+  const uint32_t* node_id;
+  const uint32_t* name_leaf;
+  const uint32_t* type;
+  const uint64_t* leaf_off;
+  const uint32_t* type_name_len;
+  uint64_t n_leaf;
+  uint32_t n_types;
+  __device__ __forceinline__ uint64_t len(uint64_t j, uint64_t* begin = nullptr) const {
+    const uint32_t id = node_id[j];
+    const uint32_t leaf = name_leaf[id], t = type[id];
+    if (leaf >= n_leaf || t >= n_types) return 0;
+    const uint64_t b = leaf_off[leaf] + type_name_len[t] + 1, e = leaf_off[leaf + 1];
+    if (begin) *begin = b;
+    return e > b ? e - b : 0;
+  }
+  __device__ __forceinline__ uint64_t operator()(uint64_t j) const { return len(j); }
+};
+
+// One thread per name: its bytes from the leaf strings to the heap; a type
+// with a name byte >= 0x80 or a newline is marked (read first: most names of
+// such a type would otherwise store to one line).
+__global__ void k_name_gather(NameSrc src, const uint8_t* leaf_bytes, const uint64_t* off, uint64_t n, uint8_t* heap,
+                              uint32_t* type_bad) {
+  for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < n; j += (uint64_t)gridDim.x * blockDim.x) {
+    uint64_t b = 0;
+    const uint64_t len = src.len(j, &b);
+    const uint64_t o = off[j];
+    uint32_t bad = 0;
+    for (uint64_t k = 0; k < len; ++k) {
+      const uint8_t ch = leaf_bytes[b + k];
+      heap[o + k] = ch;
+      bad |= (ch >= 0x80u || ch == 0x0Au) ? 1u : 0u;
+    }
+    const uint32_t t = src.type[src.node_id[j]];
+    if (bad && t < src.n_types && !type_bad[t]) type_bad[t] = 1;
+  }
+}
+
+// The range of each named type in the node list: where a run of one type
+// begins and ends, and how many runs it has (one, ids being clustered).
+__global__ void k_name_type_runs(const uint32_t* node_id, const uint32_t* type, uint64_t n, uint32_t n_types,
+                                 uint32_t* first, uint32_t* end, uint32_t* runs) {
+  for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < n; j += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t t = type[node_id[j]];
+    if (t >= n_types) continue;
+    if (j == 0 || type[node_id[j - 1]] != t) {
+      first[t] = (uint32_t)j;
+      atomicAdd(&runs[t], 1u);
+    }
+    if (j + 1 == n || type[node_id[j + 1]] != t) end[t] = (uint32_t)(j + 1);
+  }
+}
+
+__global__ void k_name_type_bytes(const uint32_t* first, const uint32_t* end, const uint32_t* runs, uint32_t n_types,
+                                  const uint64_t* off, uint64_t* bytes) {
+  for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < n_types; t += gridDim.x * blockDim.x)
+    bytes[t] = runs[t] ? off[end[t]] - off[first[t]] : 0;
+}
+
+// Walks bytes [p, e) of an image readable as aligned 32-bit words
+// (`word(k)` = bytes 4k .. 4k+3) from state entry `st`; returns the entry
+// reached (kAcceptBit set: accepted, the walk stopped there).  The four class
+// lookups of a word do not depend on the state, so only the table lookups
+// form the dependent chain: one LDS latency per byte.
+template <typename Word>
+__device__ __forceinline__ uint32_t name_walk(Word word, uint64_t p, uint64_t e, uint32_t st, const uint16_t* s_tab,
+                                              const uint8_t* s_cls) {
+  if (p >= e) return st;
+  for (uint64_t k = p >> 2; k <= (e - 1) >> 2; ++k) {
+    const uint32_t w = word(k);
+    uint32_t c[4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) c[b] = s_cls[(w >> (8 * b)) & 0xFFu];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const uint64_t q = 4 * k + b;
+      if (q >= p && q < e && !(st & kAcceptBit)) st = s_tab[st + c[b]];
+    }
+    if (st & kAcceptBit) break;
+  }
+  return st;
+}
+
+struct LdsWords {
+  const uint32_t* w;
+  __device__ __forceinline__ uint32_t operator()(uint64_t k) const { return w[k]; }
+};
+struct HeapWords {
+  const uint32_t* w;
+  __device__ __forceinline__ uint32_t operator()(uint64_t k) const { return w[k]; }
+};
+
+// flag[i] = 1 iff the automaton accepts the name of node lo + i, i < n.
+// tab: tab_n staged entries (row base of the next state | accept bit), then
+// cls: the class of each byte.  heap is 16-byte aligned and readable up to
+// the 16-byte boundary above its last byte (+ 16).
+__global__ void __launch_bounds__(kNameBlock) k_name_match(const uint8_t* __restrict__ heap,
+                                                          const uint64_t* __restrict__ off, uint64_t lo, uint64_t n,
+                                                          const uint16_t* __restrict__ tab, uint32_t tab_n,
+                                                          const uint8_t* __restrict__ cls, uint32_t start,
+                                                          uint32_t eot, uint8_t* __restrict__ flag) {
+  __shared__ uint16_t s_tab[kMaxTable];
+  __shared__ uint8_t s_cls[256];
+  __shared__ uint4 s_stage[kStageVecs];
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t i = tid; i < tab_n && i < kMaxTable; i += kNameBlock) s_tab[i] = tab[i];
+  s_cls[tid] = cls[tid];
+  const uint64_t tiles = (n + kNameBlock - 1) / kNameBlock;
+  for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const uint64_t i0 = t * kNameBlock;                                   // first name of the tile, relative to lo
+    const uint64_t cnt = n - i0 < kNameBlock ? n - i0 : kNameBlock;
+    const bool act = tid < cnt;
+    uint64_t o0 = 0, o1 = 0;
+    if (act) {
+      o0 = off[lo + i0 + tid];
+      o1 = off[lo + i0 + tid + 1];
+    }
+    const uint64_t hb = off[lo + i0], he = off[lo + i0 + cnt];            // the tile's heap bytes (block-uniform)
+    const uint64_t ab = hb & ~15ull;
+    const uint64_t span = he - ab;
+    const uint32_t staged = span < kStageCap ? (uint32_t)span : kStageCap;
+    __syncthreads();                       // the table is staged / the previous tile's walks are done
+    for (uint32_t j = tid * 16; j < staged; j += kNameBlock * 16)
+      s_stage[j >> 4] = *reinterpret_cast<const uint4*>(heap + ab + j);
+    __syncthreads();
+    if (!act) continue;
+    uint32_t st = start;
+    if (!(st & kAcceptBit)) {
+      if (o1 - ab <= kStageCap)
+        st = name_walk(LdsWords{reinterpret_cast<const uint32_t*>(s_stage)}, o0 - ab, o1 - ab, st, s_tab, s_cls);
+      else                                 // reaches past the staged bytes: walked from the heap itself
+        st = name_walk(HeapWords{reinterpret_cast<const uint32_t*>(heap)}, o0, o1, st, s_tab, s_cls);
+      if (!(st & kAcceptBit)) st = s_tab[st + eot];
+    }
+    flag[i0 + tid] = (uint8_t)(st >> 15);
+  }
+}
+
+struct ByteFlagIn {
+  const uint8_t* f;
+  __device__ __forceinline__ uint32_t operator()(uint64_t i) const { return f[i]; }
+};
+
+__global__ void k_name_emit(const uint8_t* flag, const uint32_t* pos, const uint32_t* node_id, uint64_t n,
+                            uint32_t* out) {
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+    if (flag[i]) out[pos[i]] = node_id[i];
+}
+
+void build_name_heap(Ctx& c) {
+  Index& idx = c.idx;
+  NameHeap& h = idx.names;
+  hipStream_t s = c.s;
+  const uint64_t n_atoms = idx.n_atoms, n_leaf = c.leaf_off.empty() ? 0 : c.leaf_off.size() - 1;
+  const uint32_t n_types = (uint32_t)idx.n_types;
+  const uint64_t before = idx.device_bytes;
+  h.type_lo.assign(n_types, 0);
+  h.type_hi.assign(n_types, 0);
+  h.type_bytes.assign(n_types, 0);
+  h.type_ascii.assign(n_types, 1);
+
+  // nodes in ascending id order
+  uint64_t nn = 0;
+  if (n_atoms) {
+    DBuf<uint32_t> pos(n_atoms + 1, s);
+    {
+      KScope ks("name_node_scan", 3.0 * n_atoms + 4.0 * n_atoms);
+      nn = scan_total<uint32_t>(NodeFlagIn{idx.cat}, n_atoms, pos.p, s);
+    }
+    h.node_id = dalloc<uint32_t>(idx, nn);
+    if (nn) {
+      KScope ks("k_name_nodes", 5.0 * n_atoms + 4.0 * nn);
+      hipLaunchKernelGGL(k_name_nodes, G(n_atoms), dim3(256), 0, s, (const uint8_t*)idx.cat, (const uint32_t*)pos.p,
+                         n_atoms, h.node_id);
+      DAS_HIP(hipGetLastError());
+    }
+  }
+  h.n_nodes = nn;
+  if (nn && n_types) {
+    DAS_CHECK(n_leaf > 0 && idx.type_name_len.size() == n_types, DAS_E_INTERNAL, "name heap: no leaf strings kept");
+    // name lengths -> offsets
+    DBuf<uint64_t> d_loff(n_leaf + 1, s);
+    DBuf<uint32_t> d_tnl(n_types, s);
+    DAS_HIP(hipMemcpyAsync(d_loff.p, c.leaf_off.data(), 8 * (n_leaf + 1), hipMemcpyHostToDevice, s));
+    DAS_HIP(hipMemcpyAsync(d_tnl.p, idx.type_name_len.data(), 4ull * n_types, hipMemcpyHostToDevice, s));
+    const NameSrc src{h.node_id, idx.name_leaf, idx.type, d_loff.p, d_tnl.p, n_leaf, n_types};
+    h.off = dalloc<uint64_t>(idx, nn + 1);
+    {
+      KScope ks("name_len_scan", 2.0 * 28.0 * nn + 8.0 * nn);
+      h.n_bytes = scan_total<uint64_t>(src, nn, h.off, s);
+    }
+    // the bytes (readable in whole 16-byte loads from any 16-byte boundary inside)
+    const uint64_t n_leaf_bytes = c.leaf_off[n_leaf];
+    DAS_CHECK(h.n_bytes <= n_leaf_bytes && c.leaf_bytes.size() >= n_leaf_bytes, DAS_E_INTERNAL,
+              "name heap: names exceed the leaf strings");
+    h.bytes = dalloc<uint8_t>(idx, ((h.n_bytes + 15) & ~15ull) + 16);
+    DBuf<uint8_t> d_lbytes(n_leaf_bytes ? n_leaf_bytes : 1, s);
+    if (n_leaf_bytes)
+      DAS_HIP(hipMemcpyAsync(d_lbytes.p, c.leaf_bytes.data(), n_leaf_bytes, hipMemcpyHostToDevice, s));
+    DBuf<uint32_t> tinfo(4ull * n_types, s);                      // first, end, runs, bad
+    fill_dev(tinfo.p, 0, 16ull * n_types, s);
+    uint32_t *d_first = tinfo.p, *d_end = tinfo.p + n_types, *d_runs = tinfo.p + 2ull * n_types,
+             *d_bad = tinfo.p + 3ull * n_types;
+    {
+      KScope ks("k_name_gather", 36.0 * nn + 2.0 * h.n_bytes);
+      hipLaunchKernelGGL(k_name_gather, G(nn), dim3(256), 0, s, src, (const uint8_t*)d_lbytes.p,
+                         (const uint64_t*)h.off, nn, h.bytes, d_bad);
+      DAS_HIP(hipGetLastError());
+    }
+    {
+      KScope ks("k_name_type_runs", 3.0 * 8.0 * nn);
+      hipLaunchKernelGGL(k_name_type_runs, G(nn), dim3(256), 0, s, (const uint32_t*)h.node_id,
+                         (const uint32_t*)idx.type, nn, n_types, d_first, d_end, d_runs);
+      DAS_HIP(hipGetLastError());
+    }
+    DBuf<uint64_t> d_tbytes(n_types, s);
+    {
+      KScope ks("k_name_type_bytes", 36.0 * n_types);
+      hipLaunchKernelGGL(k_name_type_bytes, G(n_types), dim3(256), 0, s, (const uint32_t*)d_first,
+                         (const uint32_t*)d_end, (const uint32_t*)d_runs, n_types, (const uint64_t*)h.off, d_tbytes.p);
+      DAS_HIP(hipGetLastError());
+    }
+    std::vector<uint32_t> ti(4ull * n_types);
+    DAS_HIP(hipMemcpyAsync(ti.data(), tinfo.p, 16ull * n_types, hipMemcpyDeviceToHost, s));
+    DAS_HIP(hipMemcpyAsync(h.type_bytes.data(), d_tbytes.p, 8ull * n_types, hipMemcpyDeviceToHost, s));
+    DAS_HIP(hipStreamSynchronize(s));
+    for (uint32_t t = 0; t < n_types; ++t) {
+      const uint32_t runs = ti[2ull * n_types + t];
+      DAS_CHECK(runs <= 1, DAS_E_UNSUPPORTED, "name heap: the nodes of a named type are not one id range");
+      if (runs) {
+        h.type_lo[t] = ti[t];
+        h.type_hi[t] = ti[n_types + t];
+        DAS_CHECK(h.type_lo[t] < h.type_hi[t] && h.type_hi[t] <= nn, DAS_E_INTERNAL, "name heap: bad type range");
+      }
+      h.type_ascii[t] = ti[3ull * n_types + t] ? 0 : 1;
+    }
+  }
+  h.device_bytes = idx.device_bytes - before;
+  h.built = true;
+}
+
+}  // namespace
+
+void ensure_name_heap(Ctx& c) {
+  DAS_CHECK(c.idx.built, DAS_E_NOT_BUILT, "index not built");
+  if (c.idx.names.built) return;
+  const size_t owned = c.idx.owned.size();
+  const uint64_t bytes = c.idx.device_bytes;
+  try {
+    build_name_heap(c);
+  } catch (...) {
+    // nothing half-built stays: the next call starts over
+    (void)hipStreamSynchronize(c.s);
+    while (c.idx.owned.size() > owned) {
+      cache_free(c.idx.owned.back());
+      c.idx.owned.pop_back();
+    }
+    c.idx.device_bytes = bytes;
+    c.idx.names = NameHeap();
+    throw;
+  }
+}
+
+void check_name_dfa(const das_name_dfa_t& d) {
+  DAS_CHECK(d.n_states >= 1 && d.n_states <= DAS_NAME_DFA_MAX_STATES, DAS_E_INVALID, "name DFA: n_states out of range");
+  DAS_CHECK(d.n_classes >= 1 && d.n_classes <= 257, DAS_E_INVALID, "name DFA: n_classes out of range");
+  DAS_CHECK((uint64_t)d.n_states * d.n_classes <= DAS_NAME_DFA_MAX_TABLE, DAS_E_INVALID,
+            "name DFA: table larger than DAS_NAME_DFA_MAX_TABLE");
+  DAS_CHECK(d.next && d.accept, DAS_E_INVALID, "name DFA: null table");
+  DAS_CHECK(d.start < d.n_states && d.eot_class < d.n_classes, DAS_E_INVALID, "name DFA: start / eot_class out of range");
+  for (int b = 0; b < 256; ++b)
+    DAS_CHECK(d.byte_class[b] < d.n_classes, DAS_E_INVALID, "name DFA: byte class out of range");
+  const uint32_t total = d.n_states * d.n_classes;
+  for (uint32_t i = 0; i < total; ++i)
+    DAS_CHECK(d.next[i] < d.n_states, DAS_E_INVALID, "name DFA: next state out of range");
+  for (uint32_t s = 0; s < d.n_states; ++s) {
+    DAS_CHECK(d.accept[s] <= 1, DAS_E_INVALID, "name DFA: accept is 0 or 1");
+    if (!d.accept[s]) continue;
+    for (uint32_t k = 0; k < d.n_classes; ++k)
+      DAS_CHECK(d.accept[d.next[s * d.n_classes + k]], DAS_E_INVALID, "name DFA: an accepting state is not absorbing");
+  }
+}
+
+uint64_t match_node_names(Ctx& c, uint32_t type_id, const das_name_dfa_t& d, uint32_t* out_ids, uint64_t cap) {
+  check_name_dfa(d);
+  DAS_CHECK(c.idx.built, DAS_E_NOT_BUILT, "index not built");
+  DAS_CHECK(type_id < c.idx.n_types, DAS_E_INVALID, "named type id out of range");
+  DAS_CHECK(out_ids || !cap, DAS_E_INVALID, "null id buffer");
+  ensure_name_heap(c);
+  const NameHeap& h = c.idx.names;
+  const uint64_t lo = h.type_lo[type_id], n = h.type_hi[type_id] - lo;
+  if (!n) return 0;
+  hipStream_t s = c.s;
+  // staged table: the row base of the next state, and whether it accepts
+  const uint32_t nc = d.n_classes, tab_n = d.n_states * nc;
+  std::vector<uint16_t> blob(tab_n + 128);                        // + 256 bytes: the class of each byte
+  for (uint32_t i = 0; i < tab_n; ++i) {
+    const uint32_t t = d.next[i];
+    blob[i] = (uint16_t)(t * nc | (d.accept[t] ? kAcceptBit : 0u));
+  }
+  std::memcpy(blob.data() + tab_n, d.byte_class, 256);
+  const uint32_t start = d.start * nc | (d.accept[d.start] ? kAcceptBit : 0u);
+  DBuf<uint16_t> d_blob(blob.size(), s);
+  DAS_HIP(hipMemcpyAsync(d_blob.p, blob.data(), 2 * blob.size(), hipMemcpyHostToDevice, s));
+  DBuf<uint8_t> flag(n, s);
+  DBuf<uint32_t> pos(n + 1, s);
+  const uint64_t tiles = (n + kNameBlock - 1) / kNameBlock;
+  const uint64_t range_bytes = h.type_bytes[type_id];
+  {
+    KScope ks("k_name_match", (double)range_bytes + 8.0 * (n + 1) + (double)n);
+    hipLaunchKernelGGL(k_name_match, dim3(grid_for(tiles, 1, 2048)), dim3(kNameBlock), 0, s, (const uint8_t*)h.bytes,
+                       (const uint64_t*)h.off, lo, n, (const uint16_t*)d_blob.p, tab_n,
+                       (const uint8_t*)(d_blob.p + tab_n), start, d.eot_class, flag.p);
+    DAS_HIP(hipGetLastError());
+  }
+  uint64_t m = 0;
+  {
+    KScope ks("name_flag_scan", 2.0 * n + 4.0 * n);
+    m = scan_total<uint32_t>(ByteFlagIn{flag.p}, n, pos.p, s);     // (waits: the staged table was read)
+  }
+  const uint64_t k = std::min(m, cap);
+  if (k) {
+    DBuf<uint32_t> ids(m, s);
+    {
+      KScope ks("k_name_emit", 5.0 * n + 8.0 * m);
+      hipLaunchKernelGGL(k_name_emit, G(n), dim3(256), 0, s, (const uint8_t*)flag.p, (const uint32_t*)pos.p,
+                         (const uint32_t*)h.node_id + lo, n, ids.p);
+      DAS_HIP(hipGetLastError());
+    }
+    DAS_HIP(hipMemcpyAsync(out_ids, ids.p, 4 * k, hipMemcpyDeviceToHost, s));
+    DAS_HIP(hipStreamSynchronize(s));
+  }
+  return m;
+}
+
+}  // namespace das

@@ -25,6 +25,7 @@ try:
 except ImportError:                         # pragma: no cover - built with the library
     _hex = None
 from .. import loader as _loader
+from .. import name_search as _name_search
 from ..expression_hasher import ExpressionHasher
 from .db_interface import UNORDERED_LINK_TYPES, WILDCARD, DBInterface
 
@@ -172,6 +173,9 @@ class HipDB(RelationalDB):
         self.pattern_black_list = []
         self.stale_pattern_keys = stale_pattern_keys
         self._stale = None              # stale_pattern_keys: pattern key -> {link handle: targets}
+        self._name_stats = {}           # named type id -> (nodes, name bytes, ascii_only), per load
+        self._name_dfas = {}            # (pattern, ascii_only) -> NameDFA or None
+        self.name_search_stats = {"device": 0, "host": 0}   # get_matched_node_name calls answered by each path
 
     def __repr__(self):
         return "<HipDB>"
@@ -199,6 +203,7 @@ class HipDB(RelationalDB):
         self._outgoing = None
         self._node_dir = None
         self._stale = None
+        self._name_stats = {}
 
     def load_metta(self, texts):
         self.load_arrays(_loader.parse_metta(texts).finish())
@@ -673,11 +678,48 @@ class HipDB(RelationalDB):
         _, _, _, _, nl = self.ctx.atoms_info(np.array([aid], dtype=np.uint32))
         return self.arrays.node_name(int(nl[0]))
 
+    def _name_type_stats(self, tid):
+        """(nodes, name bytes, ascii_only) of a named type; ascii_only: every
+        name byte of its nodes is < 0x80 and not a newline
+        (das_node_name_stats; asked once per load and type)."""
+        st = self._name_stats.get(tid)
+        if st is None:
+            st = self._name_stats[tid] = self.ctx.node_name_stats(tid)
+        return st
+
+    def _name_dfa(self, pattern, ascii_only):
+        key = (pattern, ascii_only)
+        try:
+            return self._name_dfas[key]
+        except KeyError:
+            pass
+        dfa = _name_search.compile_name_pattern(pattern, ascii_only=ascii_only)
+        if len(self._name_dfas) >= 256:
+            self._name_dfas.clear()
+        self._name_dfas[key] = dfa
+        return dfa
+
     def get_matched_node_name(self, node_type: str, substring: str) -> str:
-        """redis_mongo_db.py:287-293 (Mongo $regex on names of that type)"""
+        """redis_mongo_db.py:287-293 (Mongo $regex on names of that type).
+        The pattern is compiled to a byte DFA and the names are matched on
+        the device (das_match_node_names) where that is exact for every
+        name of the type (das_amd/name_search.py); otherwise, and with
+        DAS_NAME_SEARCH=0, `re.search` runs over a host copy of the names.
+        `name_search_stats` counts the calls each path answered."""
         tid = self.type_id.get(node_type)
         if tid is None:
             return []
+        if os.environ.get("DAS_NAME_SEARCH", "1") != "0" and isinstance(substring, str):
+            try:
+                n_nodes, _, ascii_only = self._name_type_stats(tid)
+                dfa = self._name_dfa(substring, ascii_only)
+            except NotImplementedError:     # no name heap for this index (a type's nodes not one id range)
+                dfa = None
+            if dfa is not None:
+                ids, _ = self.ctx.match_node_names(tid, dfa, cap=n_nodes)
+                self.name_search_stats["device"] += 1
+                return self.hex_of(ids) if ids.size else []
+        self.name_search_stats["host"] += 1
         dig, cat, _, ty, nl = self._host_mirror()
         sel = np.nonzero((cat == 1) & (ty == tid))[0]
         rx = re.compile(substring)

@@ -207,6 +207,40 @@ int das_incoming(das_ctx_t* ctx, uint32_t id, uint32_t* out, uint64_t cap, uint6
 /* composite-type digest -> ctype id, or -1 (templates:<composite_type_hash>) */
 int das_ctype_lookup(das_ctx_t* ctx, const uint32_t digest[4], int64_t* ctype_id);
 
+/* ---- node-name search (get_matched_node_name, redis_mongo_db.py:287-293) --- */
+/* A deterministic automaton over the UTF-8 bytes of a node name.  The class of
+ * byte b is byte_class[b]; the end of the name is the class eot_class, fed
+ * once after the last byte.  next[s * n_classes + c] is the state after class
+ * c in state s.  An accepting state must be absorbing (every transition out of
+ * it leads to an accepting state): the matcher stops at the first one.  How a
+ * pattern language maps onto this (unanchored search, anchors, code points) is
+ * the caller's business: das_amd/name_search.py compiles Python `re` patterns.
+ * Limits: n_states <= DAS_NAME_DFA_MAX_STATES, n_classes <= 257 and
+ * n_states * n_classes <= DAS_NAME_DFA_MAX_TABLE (the table is staged in LDS
+ * beside DAS_NAME_STAGE_BYTES of names). */
+typedef struct {
+  uint32_t n_states, n_classes, start, eot_class;
+  uint8_t byte_class[256];
+  const uint16_t* next;    /* n_states * n_classes */
+  const uint8_t* accept;   /* n_states; accepting states are absorbing */
+} das_name_dfa_t;
+#define DAS_NAME_DFA_MAX_STATES 1024
+#define DAS_NAME_DFA_MAX_TABLE 8192
+#define DAS_NAME_STAGE_BYTES 16384
+/* Nodes of named type `type_id` whose name, fed byte by byte and then eot_class
+ * once, ends in an accepting state: ascending id.  *n = the number of matches;
+ * min(*n, cap) ids are copied to `out_ids` (as das_incoming).  A DFA outside
+ * the limits, with an entry out of range or with an accepting state that is
+ * not absorbing returns DAS_ERR_INVALID before anything is launched.  The first
+ * call after an index build also builds the resident name heap (the node list
+ * in id order, each node's name bytes back to back, n_nodes + 1 offsets),
+ * which das_index_stats then counts in device_bytes. */
+int das_match_node_names(das_ctx_t* ctx, uint32_t type_id, const das_name_dfa_t* dfa, uint32_t* out_ids, uint64_t cap,
+                         uint64_t* n);
+/* Per named type: its number of nodes, the bytes of their names, and whether
+ * every name byte is < 0x80 and not '\n' (builds the name heap if need be). */
+int das_node_name_stats(das_ctx_t* ctx, uint32_t type_id, uint64_t* n_nodes, uint64_t* n_bytes, uint32_t* ascii_only);
+
 /* ---- query operators ----------------------------------------------------- */
 /* One Link with >= 1 wildcard, evaluated against the pattern index
  * (RedisMongoDB.get_matched_links :235-252 + Link._assign_variables :466-489).
