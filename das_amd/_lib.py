@@ -77,6 +77,9 @@ class das_name_dfa_t(C.Structure):
 
 
 NAME_STAGE_BYTES = 16384          # DAS_NAME_STAGE_BYTES: name bytes of one tile the matcher stages in LDS
+HALO_MAX_LEVELS = 8               # DAS_HALO_MAX_LEVELS
+HALO_BLOCK_ENTRIES = 1024         # DAS_HALO_BLOCK_ENTRIES: incoming-list entries one workgroup marks per pass
+PC_CHUNK_ROWS = 1024              # DAS_PC_CHUNK_ROWS: index rows one wave counts per step of a (1,2)-grounded template
 
 
 class das_plan_node_t(C.Structure):
@@ -121,6 +124,8 @@ _SIGS = {
     "das_incoming": (C.c_int, [P, C.c_uint32, P, C.c_uint64, P]),
     "das_match_node_names": (C.c_int, [P, C.c_uint32, P, P, C.c_uint64, P]),
     "das_node_name_stats": (C.c_int, [P, C.c_uint32, P, P, P]),
+    "das_halo_expand": (C.c_int, [P, P, C.c_uint64, C.c_uint32, P, P]),
+    "das_pattern_counts": (C.c_int, [P, P, P, C.c_uint64, C.POINTER(P)]),
     "das_export_outgoing": (C.c_int, [P, P, P, P, P]),
     "das_counters": (C.c_int, [P]),
     "das_scan_link": (C.c_int, [P, C.POINTER(das_link_scan_t), C.POINTER(P)]),
@@ -573,6 +578,33 @@ class Context:
         n = C.c_uint64()
         check(lib().das_match_node_names(self.h, int(type_id), C.byref(d), ptr(out), int(cap), C.byref(n)), self.h)
         return out[:min(n.value, int(cap))], n.value
+
+    def halo_expand(self, seed_ids, levels):
+        """(links, atoms): per level one-column Tables of ascending ids, the
+        links first found at that level and the atoms first reached through
+        them (das_halo_expand)."""
+        seeds = np.ascontiguousarray(np.asarray(seed_ids, dtype=np.uint32).ravel())
+        levels = int(levels)
+        if levels < 0:
+            raise ValueError("halo: negative length")
+        lo, ao = (P * max(levels, 1))(), (P * max(levels, 1))()
+        check(lib().das_halo_expand(self.h, ptr(seeds) if seeds.size else None, seeds.size, levels, lo, ao), self.h)
+        return ([Table(self, P(lo[i])) for i in range(levels)], [Table(self, P(ao[i])) for i in range(levels)])
+
+    def pattern_counts(self, links):
+        """Distinct templates of the links with their support
+        (das_pattern_counts).  links: a one-column Table of link ids (a halo
+        level, no host copy) or host ids.  Returns a (7, m) uint32 array:
+        arity, type id, t0, t1, t2 (DAS_NONE = wildcard / unused), count low
+        and high word."""
+        out = P()
+        if isinstance(links, Table):
+            check(lib().das_pattern_counts(self.h, links.h, None, 0, C.byref(out)), self.h)
+        else:
+            ids = np.ascontiguousarray(np.asarray(links, dtype=np.uint32).ravel())
+            check(lib().das_pattern_counts(self.h, None, ptr(ids) if ids.size else None, ids.size, C.byref(out)),
+                  self.h)
+        return Table(self, out).fetch()
 
     def ctype_lookup(self, digest):
         d = np.ascontiguousarray(np.asarray(digest, dtype=np.uint32))

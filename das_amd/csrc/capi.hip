@@ -533,6 +533,39 @@ int das_node_name_stats(das_ctx_t* ctx, uint32_t type_id, uint64_t* n_nodes, uin
   });
 }
 
+int das_halo_expand(das_ctx_t* ctx, const uint32_t* seed_ids, uint64_t n_seeds, uint32_t levels,
+                    das_table_t** links_out, das_table_t** atoms_out) {
+  return guarded(ctx, [&] {
+    DAS_CHECK((links_out && atoms_out) || !levels, das::DAS_E_INVALID, "null argument");
+    std::vector<std::unique_ptr<Table>> links, atoms;
+    das::halo_expand(ctx->c, seed_ids, n_seeds, levels, links, atoms);
+    for (uint32_t l = 0; l < levels; ++l) {
+      links_out[l] = wrap(std::move(links[l]));
+      atoms_out[l] = wrap(std::move(atoms[l]));
+    }
+  });
+}
+
+int das_pattern_counts(das_ctx_t* ctx, const das_table_t* links, const uint32_t* link_ids, uint64_t n,
+                       das_table_t** out) {
+  return guarded(ctx, [&] {
+    DAS_CHECK(out, das::DAS_E_INVALID, "null argument");
+    if (links) {
+      DAS_CHECK(links->t.ncols >= 1 && links->t.kind == DAS_TABLE_ORDERED, das::DAS_E_INVALID,
+                "pattern counts: the links are column 0 of an ordered table");
+      *out = wrap(das::pattern_counts(ctx->c, links->t.col(0), links->t.nrows));
+      return;
+    }
+    DAS_CHECK(link_ids || !n, das::DAS_E_INVALID, "null argument");
+    DAS_CHECK(ctx->c.idx.built, das::DAS_E_NOT_BUILT, "index not built");
+    for (uint64_t i = 0; i < n; ++i)
+      DAS_CHECK(link_ids[i] < ctx->c.idx.n_atoms, das::DAS_E_INVALID, "pattern counts: link id out of range");
+    das::DBuf<uint32_t> d(n ? n : 1, ctx->c.s);
+    if (n) DAS_HIP(hipMemcpyAsync(d.p, link_ids, 4 * n, hipMemcpyHostToDevice, ctx->c.s));
+    *out = wrap(das::pattern_counts(ctx->c, d.p, n));
+  });
+}
+
 int das_ctype_lookup(das_ctx_t* ctx, const uint32_t digest[4], int64_t* ctype_id) {
   return guarded(ctx, [&] {
     const auto& v = ctx->c.idx.ctype_digest;

@@ -99,6 +99,7 @@ struct Index {
   bool built = false;
   hipStream_t stream = nullptr;  // stream the index arrays were allocated on (caching allocator)
   uint64_t n_atoms = 0, n_nodes = 0, n_links = 0, n_types = 0;
+  uint32_t shard_world = 1;      // > 1: das_build_index_sharded (pattern rows of the owned links only)
   Digest* digest = nullptr;    // [n_atoms] by id (ids clustered by named type)
   uint32_t* by_digest = nullptr; // [n_atoms] ids in handle (digest) order
   uint8_t* cat = nullptr;      // [n_atoms]
@@ -381,6 +382,19 @@ void check_name_dfa(const das_name_dfa_t& d);
 // ids (ascending) of the nodes of `type_id` whose name `d` accepts: the
 // number of matches; min(that, cap) ids copied to the host array out_ids
 uint64_t match_node_names(Ctx& c, uint32_t type_id, const das_name_dfa_t& d, uint32_t* out_ids, uint64_t cap);
+
+// miner.hip: SimplePatternMiner's bulk steps (das_halo_expand, das_pattern_counts)
+// links[l] / atoms[l], l < levels: the links first found at level l (arity 2
+// or 3, type not black-listed, holding a frontier atom) and the targets of
+// those links not expanded before, each one ordered column of ascending ids;
+// level 0's frontier is the distinct seeds (host ids, each < n_atoms)
+void halo_expand(Ctx& c, const uint32_t* seed_ids, uint64_t n_seeds, uint32_t levels,
+                 std::vector<std::unique_ptr<Table>>& links, std::vector<std::unique_ptr<Table>>& atoms);
+// the distinct one- and two-wildcard templates of the links d_links[0..n)
+// (device ids) with len(get_links(type, None, targets)) of each: columns
+// arity, type, t0, t1, t2 (kNone = wildcard or unused), count low / high word;
+// rows ordered by (arity, type, targets)
+std::unique_ptr<Table> pattern_counts(Ctx& c, const uint32_t* d_links, uint64_t n);
 
 // Column pointers of a table (kernel argument by value).
 struct ColSet {

@@ -1592,6 +1592,7 @@ void build_index(Ctx& c, const das_atoms_t& a, uint32_t flags, uint32_t shard_ra
   free_index(c.idx);
   Index& idx = c.idx;
   idx.stream = s;
+  idx.shard_world = shard_world;
   const uint64_t nl = a.n_leaf, ne = a.n_expr, nu = nl + ne;
   DAS_CHECK(nu > 0 && nu < 0xFFFFFFF0ull, DAS_E_INVALID, "atom count out of range");
   DAS_CHECK(a.n_types < (1u << kTypeBits), DAS_E_UNSUPPORTED, "too many named types");

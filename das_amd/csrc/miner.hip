@@ -1,0 +1,689 @@
+// SimplePatternMiner's two bulk steps on the device (das_halo_expand,
+// das_pattern_counts): the halo walk of notebook cell 6 and the template
+// support counts of build_patterns (cell 5).  DESIGN.md §3d.
+//
+// Halo.  The state is four bitmaps over the atom ids (links seen / links of
+// this level / atoms expanded / atoms of this level).  A level is:
+//   scan    exclusive scan of the frontier's incoming degrees
+//   mark    workgroups take equal tiles of incoming-list ENTRIES (not atoms: a
+//           schema node sits in > 10^6 links), find each entry's atom by
+//           search in the scanned degrees, filter the link on arity and the
+//           pattern black list and set its bit (lanes of a wave that hit one
+//           word merge first; a bit already set is not set again)
+//   compact new = level & ~seen -> ascending ids; seen |= level; level = 0
+//           (count per block, then emit; 16-byte loads and stores)
+//   targets each new link's targets set their bits in the atom bitmap
+//   compact the new atoms = the next frontier, with the sum of their degrees
+// and one read-back of three counts (links, atoms, next entries).
+//
+// Counts.  Templates are generated per (link, mask), sorted and merged; one
+// thread per distinct template resolves its key (type << 32 | target) in
+// P_{a,p} -- one grounded target: the key range's width; two, where the rows
+// of a key are sorted by the other: an equal range inside it.  Targets (1,2)
+// of arity 3 are a prefix of neither index: the shorter of the two key ranges
+// is scanned for the other target, in chunks of DAS_PC_CHUNK_ROWS rows, one
+// wave per chunk and one add per wave (a short range is one chunk, a hub's
+// range is spread over the grid).
+#include <algorithm>
+#include <cstring>
+
+#include "das_internal.h"
+#include "md5.h"
+
+namespace das {
+namespace {
+
+constexpr unsigned kB = 256;
+constexpr uint32_t kHaloTile = DAS_HALO_BLOCK_ENTRIES;    // entries of one workgroup pass
+constexpr uint32_t kPcChunk = DAS_PC_CHUNK_ROWS;          // rows of one wave step
+constexpr uint32_t kBitBlocks = 1024;                     // workgroups of a bitmap compaction (at most)
+constexpr uint32_t kInvalidKey = 1u << 26;                // sort key of a dropped template (after every arity << 24 | type)
+static_assert(kHaloTile % kB == 0 && kPcChunk % 64 == 0, "tiles are whole waves");
+
+inline dim3 G(uint64_t n, unsigned cap = 65535u * 8u) { return dim3(grid_for(n, kB, cap)); }
+
+// ---------------------------------------------------------------------------
+// halo
+// ---------------------------------------------------------------------------
+struct DegIn {
+  const uint32_t* frontier;
+  const uint32_t* in_off;
+  __device__ __forceinline__ uint64_t operator()(uint64_t i) const {
+    const uint32_t a = frontier[i];
+    return (uint64_t)(in_off[a + 1] - in_off[a]);
+  }
+  static std::string name() { return "DegIn"; }
+};
+
+// bits of the seeds in the level's atom bitmap (ids checked on the host)
+__global__ void k_halo_seed_bits(const uint32_t* seeds, uint64_t n, uint32_t* level_atoms, unsigned long long* deg_sum) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *deg_sum = 0;
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t a = seeds[i];
+    atomicOr(&level_atoms[a >> 5], 1u << (a & 31));
+  }
+}
+
+// eoff: exclusive scan of the frontier's incoming degrees, E their sum.
+// Entry e belongs to the last frontier atom a with eoff[a] <= e.
+__global__ void __launch_bounds__(kB) k_halo_mark_links(const uint32_t* __restrict__ frontier, uint64_t nf,
+                                                       const uint64_t* __restrict__ eoff, uint64_t E,
+                                                       const uint32_t* __restrict__ in_off,
+                                                       const uint32_t* __restrict__ in_link,
+                                                       const uint32_t* __restrict__ arity,
+                                                       const uint32_t* __restrict__ type,
+                                                       const uint8_t* __restrict__ blocked, uint32_t n_types,
+                                                       uint64_t n_atoms, uint32_t* level_links) {
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t tiles = (E + kHaloTile - 1) / kHaloTile;
+  for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const uint64_t wbase = t * kHaloTile + (uint64_t)wave * (kHaloTile / (kB / 64));
+    for (uint32_t it = 0; it < kHaloTile / kB; ++it) {
+      const uint64_t e = wbase + it * 64 + lane;
+      uint32_t word = kNone, bits = 0;
+      if (e < E) {
+        uint64_t lo = 0, hi = nf;
+        while (lo < hi) {
+          const uint64_t mid = (lo + hi) >> 1;
+          if (eoff[mid] <= e) lo = mid + 1; else hi = mid;
+        }
+        const uint64_t a = lo - 1;                       // eoff[0] = 0 <= e: lo >= 1
+        const uint32_t atom = frontier[a];
+        const uint32_t link = in_link[(uint64_t)in_off[atom] + (e - eoff[a])];
+        if (link < n_atoms) {
+          const uint32_t ar = arity[link], ty = type[link];
+          if ((ar == 2 || ar == 3) && ty < n_types && !(blocked && blocked[ty])) {
+            word = link >> 5;
+            bits = 1u << (link & 31);
+            if (level_links[word] & bits) {              // set already (a stale read only repeats the atomic)
+              word = kNone;
+              bits = 0;
+            }
+          }
+        }
+      }
+      // an atom's list is sorted by link id: the lanes of one word are
+      // neighbours, and the first of them sets the bits of all
+      const uint32_t prev = __shfl_up(word, 1, 64);
+      uint32_t acc = bits;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t ow = __shfl_down(word, d, 64), ob = __shfl_down(acc, d, 64);
+        if (lane + d < 64 && ow == word) acc |= ob;
+      }
+      if (bits && (lane == 0 || prev != word)) atomicOr(&level_links[word], acc);
+    }
+  }
+}
+
+// every target of the n = *n_links new links that was in no frontier yet
+__global__ void k_halo_mark_targets(const uint32_t* __restrict__ links, const unsigned long long* n_links,
+                                    const uint64_t* __restrict__ tgt_off, const uint32_t* __restrict__ tgt,
+                                    uint64_t n_atoms, const uint32_t* __restrict__ seen_atoms, uint32_t* level_atoms,
+                                    unsigned long long* deg_sum) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *deg_sum = 0;     // the compaction after this kernel adds to it
+  const uint64_t n = *n_links;
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t l = links[i];
+    const uint64_t b = tgt_off[l];
+    const uint32_t k = (uint32_t)min((uint64_t)3, tgt_off[l + 1] - b);   // arity 2 or 3 (mark_links)
+    for (uint32_t p = 0; p < k; ++p) {
+      const uint32_t t = tgt[b + p];
+      if (t >= n_atoms) continue;
+      const uint32_t w = t >> 5, bit = 1u << (t & 31);
+      if ((seen_atoms[w] & bit) || (level_atoms[w] & bit)) continue;     // (a stale read only repeats the atomic)
+      atomicOr(&level_atoms[w], bit);
+    }
+  }
+}
+
+__device__ __forceinline__ uint32_t popc_new(const uint4& L, const uint4& S) {
+  return __popc(L.x & ~S.x) + __popc(L.y & ~S.y) + __popc(L.z & ~S.z) + __popc(L.w & ~S.w);
+}
+
+// counts[b] = bits of level & ~seen in block b's vectors [b * per, (b + 1) * per)
+__global__ void __launch_bounds__(kB) k_bits_count(const uint4* __restrict__ level, const uint4* __restrict__ seen,
+                                                  uint64_t nvec, uint64_t per, uint32_t* counts) {
+  __shared__ uint32_t s_w[kB / 64];
+  const uint64_t v0 = blockIdx.x * per, v1 = min(v0 + per, nvec);
+  uint32_t local = 0;
+  for (uint64_t v = v0 + threadIdx.x; v < v1; v += kB) {
+    const uint4 L = level[v];
+    if (L.x | L.y | L.z | L.w) local += popc_new(L, seen[v]);
+  }
+  local = wave_reduce_sum(local);
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = local;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t t = 0;
+    for (unsigned w = 0; w < kB / 64; ++w) t += s_w[w];
+    counts[blockIdx.x] = t;
+  }
+}
+
+// out: the ids of level & ~seen, ascending; seen |= level; level = 0; *total
+// = their number; with in_off, *deg_sum += the incoming degrees of the ids.
+__global__ void __launch_bounds__(kB) k_bits_emit(uint4* level, uint4* seen, uint64_t nvec, uint64_t per,
+                                                 const uint32_t* __restrict__ counts, uint32_t* out,
+                                                 unsigned long long* total, const uint32_t* __restrict__ in_off,
+                                                 unsigned long long* deg_sum) {
+  __shared__ uint32_t s_w[kB / 64];
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t pre = 0;
+  for (uint32_t i = threadIdx.x; i < blockIdx.x; i += kB) pre += counts[i];
+  pre = wave_reduce_sum(pre);
+  if (lane == 0) s_w[wave] = pre;
+  __syncthreads();
+  uint32_t run = 0;
+  for (unsigned w = 0; w < kB / 64; ++w) run += s_w[w];
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total = (unsigned long long)run + counts[blockIdx.x];
+  __syncthreads();
+  const uint64_t v0 = blockIdx.x * per, v1 = min(v0 + per, nvec);
+  unsigned long long deg = 0;
+  for (uint64_t tb = v0; tb < v1; tb += kB) {
+    const uint64_t v = tb + threadIdx.x;
+    uint32_t nw[4] = {0, 0, 0, 0};
+    if (v < v1) {
+      const uint4 L = level[v];
+      if (L.x | L.y | L.z | L.w) {
+        const uint4 S = seen[v];
+        nw[0] = L.x & ~S.x; nw[1] = L.y & ~S.y; nw[2] = L.z & ~S.z; nw[3] = L.w & ~S.w;
+        seen[v] = make_uint4(S.x | L.x, S.y | L.y, S.z | L.z, S.w | L.w);
+        level[v] = make_uint4(0, 0, 0, 0);
+      }
+    }
+    const uint32_t cnt = __popc(nw[0]) + __popc(nw[1]) + __popc(nw[2]) + __popc(nw[3]);
+    const uint32_t inc = wave_incl_sum_u32(cnt);
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    uint32_t wpre = 0, all = 0;
+    for (unsigned w = 0; w < kB / 64; ++w) {
+      wpre += w < wave ? s_w[w] : 0u;
+      all += s_w[w];
+    }
+    if (cnt) {
+      uint32_t pos = run + wpre + inc - cnt;
+      const uint32_t base = (uint32_t)(v * 128);
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        uint32_t bits = nw[w];
+        while (bits) {
+          const uint32_t id = base + 32 * w + (uint32_t)(__ffs(bits) - 1);
+          bits &= bits - 1;
+          out[pos++] = id;
+          if (in_off) deg += in_off[id + 1] - in_off[id];
+        }
+      }
+    }
+    run += all;
+    __syncthreads();
+  }
+  if (in_off) {
+    deg = wave_reduce_sum(deg);
+    if (lane == 0 && deg) atomicAdd(deg_sum, deg);
+  }
+}
+
+struct HaloState {
+  uint64_t nvec = 0, per = 0;
+  unsigned blocks = 1;
+  DBuf<uint32_t> bits;            // links seen | links level | atoms seen | atoms level
+  DBuf<uint32_t> counts;          // per-block counts of a compaction
+  DBuf<unsigned long long> ctr;   // new links, new atoms, next entries
+  uint4* vec(int k) const { return reinterpret_cast<uint4*>(bits.p) + k * nvec; }
+  uint32_t* words(int k) const { return bits.p + 4 * k * nvec; }
+};
+
+// new = level & ~seen of bitmap pair (k_seen, k_seen + 1) -> out, ascending
+void compact_bits(Ctx& c, HaloState& h, int k_seen, uint32_t* out, unsigned long long* total, const uint32_t* in_off) {
+  {
+    ProfScope ps(c, "k_bits_count", 32.0 * h.nvec);
+    hipLaunchKernelGGL(k_bits_count, dim3(h.blocks), dim3(kB), 0, c.s, (const uint4*)h.vec(k_seen + 1),
+                       (const uint4*)h.vec(k_seen), h.nvec, h.per, h.counts.p);
+    DAS_HIP(hipGetLastError());
+  }
+  ProfScope ps(c, "k_bits_emit", 32.0 * h.nvec);
+  hipLaunchKernelGGL(k_bits_emit, dim3(h.blocks), dim3(kB), 0, c.s, h.vec(k_seen + 1), h.vec(k_seen), h.nvec, h.per,
+                     (const uint32_t*)h.counts.p, out, total, in_off, h.ctr.p + 2);
+  DAS_HIP(hipGetLastError());
+}
+
+void read_counters3(Ctx& c, const HaloState& h, uint64_t out[3]) {
+  DAS_HIP(hipMemcpyAsync(c.scratch.h, h.ctr.p, 24, hipMemcpyDeviceToHost, c.s));
+  DAS_HIP(hipStreamSynchronize(c.s));
+  count_readback();
+  for (int i = 0; i < 3; ++i) out[i] = c.scratch.h[i];
+}
+
+std::unique_ptr<Table> id_column(Ctx& c, const uint32_t* d_ids, uint64_t n, uint64_t n_atoms) {
+  const int32_t var0 = 0;
+  auto t = new_table(c, DAS_TABLE_ORDERED, 1, &var0, n);
+  t->nrows = n;
+  t->sorted_col = 0;
+  if (n_atoms) t->hi[0] = (uint32_t)(n_atoms - 1);
+  if (n) copy_dev(t->col(0), d_ids, 4 * n, c.s);
+  return t;
+}
+
+void miner_check(const Ctx& c) {
+  DAS_CHECK(c.idx.built, DAS_E_NOT_BUILT, "index not built");
+  DAS_CHECK(c.idx.shard_world <= 1, DAS_E_UNSUPPORTED, "pattern miner: a sharded index holds only its own links' rows");
+}
+
+// device copy of the black-list flags per named type (null: no list)
+void upload_blocked(Ctx& c, DBuf<uint8_t>& d) {
+  const Index& idx = c.idx;
+  if (!idx.no_pattern_any || idx.no_pattern.empty()) return;
+  d.alloc(idx.no_pattern.size(), c.s);
+  DAS_HIP(hipMemcpyAsync(d.p, idx.no_pattern.data(), idx.no_pattern.size(), hipMemcpyHostToDevice, c.s));
+}
+
+}  // namespace
+
+void halo_expand(Ctx& c, const uint32_t* seed_ids, uint64_t n_seeds, uint32_t levels,
+                 std::vector<std::unique_ptr<Table>>& links, std::vector<std::unique_ptr<Table>>& atoms) {
+  miner_check(c);
+  Index& idx = c.idx;
+  DAS_CHECK(levels <= DAS_HALO_MAX_LEVELS, DAS_E_INVALID, "halo: more than DAS_HALO_MAX_LEVELS levels");
+  DAS_CHECK(seed_ids || !n_seeds, DAS_E_INVALID, "halo: null seed ids");
+  DAS_CHECK(n_seeds < (1ull << 32), DAS_E_INVALID, "halo: too many seeds");
+  for (uint64_t i = 0; i < n_seeds; ++i)
+    DAS_CHECK(seed_ids[i] < idx.n_atoms, DAS_E_INVALID, "halo: seed id out of range");
+  links.clear();
+  atoms.clear();
+  hipStream_t s = c.s;
+  const uint64_t n_atoms = idx.n_atoms;
+  uint64_t nf = 0, E = 0;
+  HaloState h;
+  DBuf<uint32_t> d_seeds, scratch_l, scratch_a, frontier0;
+  DBuf<uint8_t> blocked;
+  DBuf<uint64_t> eoff;
+  const uint32_t* frontier = nullptr;
+  if (levels && n_seeds) {
+    h.nvec = (n_atoms + 127) / 128;
+    h.blocks = grid_for(h.nvec, kB, kBitBlocks);
+    h.per = (h.nvec + h.blocks - 1) / h.blocks;
+    h.bits.alloc(16 * h.nvec, s);
+    h.counts.alloc(h.blocks, s);
+    h.ctr.alloc(4, s);
+    fill_dev(h.bits.p, 0, 64 * h.nvec, s);
+    fill_dev(h.ctr.p, 0, 32, s);
+    upload_blocked(c, blocked);
+    scratch_l.alloc(std::max<uint64_t>(idx.n_links, 1), s);
+    scratch_a.alloc(n_atoms, s);
+    d_seeds.alloc(n_seeds, s);
+    DAS_HIP(hipMemcpyAsync(d_seeds.p, seed_ids, 4 * n_seeds, hipMemcpyHostToDevice, s));
+    {
+      ProfScope ps(c, "k_halo_seed_bits", 8.0 * n_seeds);
+      hipLaunchKernelGGL(k_halo_seed_bits, G(n_seeds, 1024), dim3(kB), 0, s, (const uint32_t*)d_seeds.p, n_seeds,
+                         h.words(3), h.ctr.p + 2);
+      DAS_HIP(hipGetLastError());
+    }
+    compact_bits(c, h, 2, scratch_a.p, h.ctr.p + 1, idx.in_off);
+    uint64_t r[3];
+    read_counters3(c, h, r);
+    nf = r[1];
+    E = r[2];
+    frontier0.alloc(std::max<uint64_t>(nf, 1), s);
+    if (nf) copy_dev(frontier0.p, scratch_a.p, 4 * nf, s);
+    frontier = frontier0.p;
+  }
+  for (uint32_t lv = 0; lv < levels; ++lv) {
+    uint64_t nl = 0, na = 0, e_next = 0;
+    if (nf && E) {
+      DAS_CHECK(E <= idx.in_total, DAS_E_INTERNAL, "halo: more entries than incoming links");
+      if (eoff.n < nf) eoff.alloc(nf, s);
+      exclusive_scan_fn<uint64_t>(DegIn{frontier, idx.in_off}, nf, eoff.p, s);
+      {
+        ProfScope ps(c, "k_halo_mark_links", 12.0 * E + 16.0 * nf);
+        hipLaunchKernelGGL(k_halo_mark_links, dim3(grid_for(E, kHaloTile, 4096)), dim3(kB), 0, s, frontier, nf,
+                           (const uint64_t*)eoff.p, E, (const uint32_t*)idx.in_off, (const uint32_t*)idx.in_link,
+                           (const uint32_t*)idx.arity, (const uint32_t*)idx.type, (const uint8_t*)blocked.p,
+                           (uint32_t)idx.n_types, n_atoms, h.words(1));
+        DAS_HIP(hipGetLastError());
+      }
+      compact_bits(c, h, 0, scratch_l.p, h.ctr.p + 0, nullptr);
+      const uint64_t bound = std::min<uint64_t>(E, idx.n_links);       // new links at most
+      {
+        ProfScope ps(c, "k_halo_mark_targets", 32.0 * bound);
+        hipLaunchKernelGGL(k_halo_mark_targets, G(bound, 4096), dim3(kB), 0, s, (const uint32_t*)scratch_l.p,
+                           (const unsigned long long*)h.ctr.p, (const uint64_t*)idx.tgt_off,
+                           (const uint32_t*)idx.tgt, n_atoms, (const uint32_t*)h.words(2), h.words(3), h.ctr.p + 2);
+        DAS_HIP(hipGetLastError());
+      }
+      compact_bits(c, h, 2, scratch_a.p, h.ctr.p + 1, idx.in_off);
+      uint64_t r[3];
+      read_counters3(c, h, r);
+      nl = r[0];
+      na = r[1];
+      e_next = r[2];
+      DAS_CHECK(nl <= idx.n_links && na <= n_atoms, DAS_E_INTERNAL, "halo: level larger than the index");
+    }
+    links.push_back(id_column(c, scratch_l.p, nl, n_atoms));
+    atoms.push_back(id_column(c, scratch_a.p, na, n_atoms));
+    frontier = atoms.back()->col(0);
+    nf = na;
+    E = e_next;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// template support
+// ---------------------------------------------------------------------------
+namespace {
+
+struct PView {
+  const uint64_t* ukey;
+  const uint64_t* uoff;
+  uint64_t nkeys;
+  const uint32_t* col[3];      // t0 .. t2 of the rows
+};
+struct PcIndex {
+  PView p2[2], p3[3];
+};
+PView view_of(const PosIndex& P, int arity) {
+  PView v{};
+  v.ukey = P.ukey;
+  v.uoff = P.uoff;
+  v.nkeys = P.ukey && P.uoff ? P.nkeys : 0;
+  for (int k = 0; k < arity; ++k) v.col[k] = P.t.data ? P.t.col(1 + k) : nullptr;
+  return v;
+}
+
+// rows [lo, hi) of key (ty, t); false: no such key
+__device__ __forceinline__ bool key_run(const PView& P, uint32_t ty, uint32_t t, uint64_t& lo, uint64_t& hi) {
+  const uint64_t key = ((uint64_t)ty << 32) | t;
+  uint64_t a = 0, b = P.nkeys;
+  while (a < b) {
+    const uint64_t mid = (a + b) >> 1;
+    if (P.ukey[mid] < key) a = mid + 1; else b = mid;
+  }
+  lo = hi = 0;
+  if (a >= P.nkeys || P.ukey[a] != key) return false;
+  lo = P.uoff[a];
+  hi = P.uoff[a + 1];
+  return true;
+}
+// first row of [lo, hi) whose col value is >= v (col ascending there)
+__device__ __forceinline__ uint64_t lower_row(const uint32_t* col, uint64_t lo, uint64_t hi, uint64_t v) {
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if ((uint64_t)col[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// Row i * 6 + j: template j of link i (build_patterns: arity 2 -> 2, arity 3
+// -> 6; bit p of the mask = target p grounded).  k0 = arity << 24 | type, or
+// kInvalidKey: no such template, or a grounded target that is not a node.
+// A wildcard or unused position holds n_atoms (sorts after every id).
+__global__ void k_pc_templates(const uint32_t* __restrict__ links, uint64_t n, uint64_t n_atoms, uint32_t n_types,
+                               const uint8_t* __restrict__ cat, const uint32_t* __restrict__ arity,
+                               const uint32_t* __restrict__ type, const uint64_t* __restrict__ tgt_off,
+                               const uint32_t* __restrict__ tgt, uint32_t* k0, uint32_t* t0, uint32_t* t1,
+                               uint32_t* t2) {
+  const uint64_t R = n * 6;
+  const uint32_t W = (uint32_t)n_atoms;
+  for (uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; r < R; r += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t i = r / 6;
+    const uint32_t j = (uint32_t)(r % 6);
+    const uint32_t l = links[i];
+    uint32_t key = kInvalidKey, T[3] = {W, W, W};
+    if (l < n_atoms && cat[l] == CAT_LINK) {
+      const uint32_t ar = arity[l], ty = type[l];
+      const uint64_t o = tgt_off[l];
+      uint32_t mask = 0;
+      if (ar == 2 && j < 2) mask = j == 0 ? 2u : 1u;
+      else if (ar == 3) mask = j == 0 ? 6u : j == 1 ? 5u : j == 2 ? 3u : j == 3 ? 4u : j == 4 ? 2u : 1u;
+      if (mask && ty < n_types && tgt_off[l + 1] - o == ar) {
+        bool ok = true;
+        for (uint32_t p = 0; p < ar; ++p) {
+          if (!((mask >> p) & 1u)) continue;
+          const uint32_t t = tgt[o + p];
+          if (t >= n_atoms || cat[t] != CAT_NODE) ok = false;   // get_node_type raises: the template is dropped
+          T[p] = t;
+        }
+        if (ok) key = (ar << 24) | ty;
+        else T[0] = T[1] = T[2] = W;
+      }
+    }
+    k0[r] = key;
+    t0[r] = T[0];
+    t1[r] = T[1];
+    t2[r] = T[2];
+  }
+}
+
+// flag[i] = 1: sorted row i is a template and differs from the row before it
+__global__ void k_pc_flags(const uint32_t* __restrict__ k0, const uint32_t* __restrict__ t0,
+                           const uint32_t* __restrict__ t1, const uint32_t* __restrict__ t2,
+                           const uint32_t* __restrict__ perm, uint64_t R, uint32_t* flag) {
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < R; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t r = perm[i];
+    uint32_t f = k0[r] != kInvalidKey ? 1u : 0u;
+    if (f && i > 0) {
+      const uint32_t q = perm[i - 1];
+      if (k0[q] == k0[r] && t0[q] == t0[r] && t1[q] == t1[r] && t2[q] == t2[r]) f = 0;
+    }
+    flag[i] = f;
+  }
+}
+
+__global__ void k_pc_emit(const uint32_t* __restrict__ k0, const uint32_t* __restrict__ t0,
+                          const uint32_t* __restrict__ t1, const uint32_t* __restrict__ t2,
+                          const uint32_t* __restrict__ perm, const uint32_t* __restrict__ flag,
+                          const uint32_t* __restrict__ pos, uint64_t R, uint32_t* o_ar, uint32_t* o_ty, uint32_t* o_t0,
+                          uint32_t* o_t1, uint32_t* o_t2) {
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < R; i += (uint64_t)gridDim.x * blockDim.x) {
+    if (!flag[i]) continue;
+    const uint32_t r = perm[i], o = pos[i];
+    o_ar[o] = k0[r] >> 24;
+    o_ty[o] = k0[r] & 0xFFFFFFu;
+    o_t0[o] = t0[r];
+    o_t1[o] = t1[r];
+    o_t2[o] = t2[r];
+  }
+}
+
+__device__ __forceinline__ bool digest_less(const Digest& a, const Digest& b) {
+  return a.hi() != b.hi() ? a.hi() < b.hi() : a.lo() < b.lo();
+}
+
+// One thread per template: its count where a key range answers it; else the
+// range to scan: rows [p_lo, p_lo + p_len) of P_{3,p_sel}, counting those
+// whose other grounded target equals p_val, in nch chunks.
+__global__ void k_pc_resolve(uint64_t m, uint32_t W, const uint32_t* __restrict__ c_ar,
+                             const uint32_t* __restrict__ c_ty, const uint32_t* __restrict__ c_t0,
+                             const uint32_t* __restrict__ c_t1, const uint32_t* __restrict__ c_t2, PcIndex X,
+                             const uint8_t* __restrict__ blocked, uint32_t unord0, uint32_t unord1,
+                             const Digest* __restrict__ digest, unsigned long long* count, uint64_t* nch,
+                             uint64_t* p_lo, uint64_t* p_len, uint32_t* p_sel, uint32_t* p_val) {
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < m; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t ar = c_ar[i], ty = c_ty[i];
+    uint32_t T[3] = {c_t0[i], c_t1[i], c_t2[i]};
+    unsigned long long cnt = 0;
+    uint64_t chunks = 0, lo = 0, hi = 0;
+    uint32_t sel = 0, val = 0;
+    if (!(blocked && blocked[ty]) && (ar == 2 || ar == 3)) {
+      uint32_t g[3], ng = 0;
+      for (uint32_t p = 0; p < ar; ++p)
+        if (T[p] != W) g[ng++] = T[p];
+      if (ty == unord0 || ty == unord1) {
+        // the reference's key: sorted(handles), '*' before every hex digit
+        if (ng == 2 && digest_less(digest[g[1]], digest[g[0]])) {
+          const uint32_t x = g[0];
+          g[0] = g[1];
+          g[1] = x;
+        }
+        for (uint32_t p = 0; p < ar; ++p) T[p] = p + ng < ar ? W : g[p + ng - ar];
+      }
+      if (ng == 1) {
+        uint32_t p = 0;
+        while (T[p] == W) ++p;
+        if (key_run(ar == 2 ? X.p2[p] : X.p3[p], ty, T[p], lo, hi)) cnt = hi - lo;
+      } else if (ng == 2 && ar == 3) {
+        if (T[2] == W) {                       // (0,1): rows of key t0 are sorted by t1
+          if (key_run(X.p3[0], ty, T[0], lo, hi))
+            cnt = lower_row(X.p3[0].col[1], lo, hi, (uint64_t)T[1] + 1) - lower_row(X.p3[0].col[1], lo, hi, T[1]);
+        } else if (T[1] == W) {                // (0,2): rows of key t2 are sorted by t0
+          if (key_run(X.p3[2], ty, T[2], lo, hi))
+            cnt = lower_row(X.p3[2].col[0], lo, hi, (uint64_t)T[0] + 1) - lower_row(X.p3[2].col[0], lo, hi, T[0]);
+        } else {                               // (1,2): the shorter key range, filtered on the other target
+          uint64_t lo1, hi1, lo2, hi2;
+          if (key_run(X.p3[1], ty, T[1], lo1, hi1) && key_run(X.p3[2], ty, T[2], lo2, hi2)) {
+            if (hi1 - lo1 <= hi2 - lo2) { sel = 1; val = T[2]; lo = lo1; hi = hi1; }
+            else { sel = 2; val = T[1]; lo = lo2; hi = hi2; }
+            chunks = (hi - lo + kPcChunk - 1) / kPcChunk;
+          }
+        }
+      }
+    }
+    count[i] = cnt;
+    nch[i] = chunks;
+    p_lo[i] = lo;
+    p_len[i] = chunks ? hi - lo : 0;
+    p_sel[i] = sel;
+    p_val[i] = val;
+  }
+}
+
+// choff: exclusive scan of nch.  One wave per chunk.
+__global__ void __launch_bounds__(kB) k_pc_scan(uint64_t m, const uint64_t* __restrict__ choff,
+                                               const uint64_t* __restrict__ nch, const uint64_t* __restrict__ p_lo,
+                                               const uint64_t* __restrict__ p_len, const uint32_t* __restrict__ p_sel,
+                                               const uint32_t* __restrict__ p_val, const uint32_t* __restrict__ col31_t2,
+                                               const uint32_t* __restrict__ col32_t1, unsigned long long* count) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t total = choff[m - 1] + nch[m - 1];
+  const uint64_t nwaves = (uint64_t)gridDim.x * (kB / 64);
+  for (uint64_t ch = (uint64_t)blockIdx.x * (kB / 64) + (threadIdx.x >> 6); ch < total; ch += nwaves) {
+    uint64_t a = 0, b = m;                     // the last template with choff <= ch owns the chunk
+    while (a < b) {
+      const uint64_t mid = (a + b) >> 1;
+      if (choff[mid] <= ch) a = mid + 1; else b = mid;
+    }
+    const uint64_t i = a - 1;
+    const uint64_t r0 = p_lo[i] + (ch - choff[i]) * kPcChunk;
+    const uint64_t r1 = min(r0 + kPcChunk, p_lo[i] + p_len[i]);
+    const uint32_t* col = p_sel[i] == 1 ? col31_t2 : col32_t1;
+    const uint32_t val = p_val[i];
+    uint32_t cnt = 0;
+    for (uint64_t r = r0 + lane; r < r1; r += 64) cnt += col[r] == val ? 1u : 0u;
+    cnt = wave_reduce_sum(cnt);
+    if (lane == 0 && cnt) atomicAdd(&count[i], (unsigned long long)cnt);
+  }
+}
+
+__global__ void k_pc_finish(uint64_t m, uint32_t W, const unsigned long long* __restrict__ count, uint32_t* t0,
+                            uint32_t* t1, uint32_t* t2, uint32_t* c_lo, uint32_t* c_hi) {
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < m; i += (uint64_t)gridDim.x * blockDim.x) {
+    if (t0[i] == W) t0[i] = kNone;
+    if (t1[i] == W) t1[i] = kNone;
+    if (t2[i] == W) t2[i] = kNone;
+    c_lo[i] = (uint32_t)count[i];
+    c_hi[i] = (uint32_t)(count[i] >> 32);
+  }
+}
+
+uint32_t type_named(const Index& idx, const char* name) {
+  Digest d;
+  md5::digest_bytes(reinterpret_cast<const uint8_t*>(name), std::strlen(name), d.w);
+  for (uint32_t t = 0; t < idx.type_digest.size(); ++t)
+    if (std::memcmp(d.w, idx.type_digest[t].w, 16) == 0) return t;
+  return kNone;
+}
+
+}  // namespace
+
+std::unique_ptr<Table> pattern_counts(Ctx& c, const uint32_t* d_links, uint64_t n) {
+  miner_check(c);
+  Index& idx = c.idx;
+  DAS_CHECK(n < (1ull << 32) / 6, DAS_E_UNSUPPORTED, "pattern counts: too many links in one call");
+  hipStream_t s = c.s;
+  const int32_t vars[7] = {0, 1, 2, 3, 4, 5, 6};
+  const uint64_t n_atoms = idx.n_atoms, R = 6 * n;
+  const uint32_t W = (uint32_t)n_atoms;
+  uint64_t m = 0;
+  DBuf<uint32_t> rows, perm, flag, pos;
+  if (R) {
+    rows.alloc(4 * R, s);
+    uint32_t *k0 = rows.p, *t0 = rows.p + R, *t1 = rows.p + 2 * R, *t2 = rows.p + 3 * R;
+    {
+      ProfScope ps(c, "k_pc_templates", 4.0 * n + 6.0 * n * 16.0 + n * (9.0 + 8.0 + 12.0 + 3.0));
+      hipLaunchKernelGGL(k_pc_templates, G(R), dim3(kB), 0, s, d_links, n, n_atoms, (uint32_t)idx.n_types,
+                         (const uint8_t*)idx.cat, (const uint32_t*)idx.arity, (const uint32_t*)idx.type,
+                         (const uint64_t*)idx.tgt_off, (const uint32_t*)idx.tgt, k0, t0, t1, t2);
+      DAS_HIP(hipGetLastError());
+    }
+    perm.alloc(R, s);
+    ColSet cs{};
+    cs.n = 4;
+    cs.c[0] = k0; cs.c[1] = t0; cs.c[2] = t1; cs.c[3] = t2;
+    sort_perm(cs, R, perm.p, std::max(27, bits_for(n_atoms)), s);
+    flag.alloc(R, s);
+    pos.alloc(R + 1, s);
+    {
+      ProfScope ps(c, "k_pc_flags", 40.0 * R);
+      hipLaunchKernelGGL(k_pc_flags, G(R), dim3(kB), 0, s, (const uint32_t*)k0, (const uint32_t*)t0,
+                         (const uint32_t*)t1, (const uint32_t*)t2, (const uint32_t*)perm.p, R, flag.p);
+      DAS_HIP(hipGetLastError());
+    }
+    m = scan_total<uint32_t>(SpanIn<uint32_t>{flag.p}, R, pos.p, s);
+  }
+  auto out = new_table(c, DAS_TABLE_ORDERED, 7, vars, m);
+  out->nrows = m;
+  if (!m) return out;
+  {
+    const uint32_t *k0 = rows.p, *t0 = rows.p + R, *t1 = rows.p + 2 * R, *t2 = rows.p + 3 * R;
+    ProfScope ps(c, "k_pc_emit", 12.0 * R + 36.0 * m);
+    hipLaunchKernelGGL(k_pc_emit, G(R), dim3(kB), 0, s, k0, t0, t1, t2, (const uint32_t*)perm.p,
+                       (const uint32_t*)flag.p, (const uint32_t*)pos.p, R, out->col(0), out->col(1), out->col(2),
+                       out->col(3), out->col(4));
+    DAS_HIP(hipGetLastError());
+  }
+  PcIndex X{};
+  for (int p = 0; p < 2; ++p) X.p2[p] = view_of(idx.pidx[2][p], 2);
+  for (int p = 0; p < 3; ++p) X.p3[p] = view_of(idx.pidx[3][p], 3);
+  DBuf<uint8_t> blocked;
+  upload_blocked(c, blocked);
+  DBuf<unsigned long long> count(m, s);
+  DBuf<uint64_t> probe(4 * m, s);                     // nch, choff, p_lo, p_len
+  DBuf<uint32_t> psv(2 * m, s);                       // p_sel, p_val
+  uint64_t *nch = probe.p, *choff = probe.p + m, *p_lo = probe.p + 2 * m, *p_len = probe.p + 3 * m;
+  {
+    // per template: its row, ~2 key searches, the probe record
+    ProfScope ps(c, "k_pc_resolve", m * (20.0 + 2.0 * 8.0 * 24.0 + 48.0));
+    hipLaunchKernelGGL(k_pc_resolve, G(m), dim3(kB), 0, s, m, W, (const uint32_t*)out->col(0),
+                       (const uint32_t*)out->col(1), (const uint32_t*)out->col(2), (const uint32_t*)out->col(3),
+                       (const uint32_t*)out->col(4), X, (const uint8_t*)blocked.p, type_named(idx, "Similarity"),
+                       type_named(idx, "Set"), (const Digest*)idx.digest, count.p, nch, p_lo, p_len, psv.p,
+                       psv.p + m);
+    DAS_HIP(hipGetLastError());
+  }
+  if (X.p3[1].nkeys && X.p3[2].nkeys) {
+    exclusive_scan<uint64_t>(nch, m, choff, s);
+    {
+      // the scope counts the probe records; the rows scanned are known on
+      // the device only and are added below when profiling is on (the
+      // summing scan is then timed as a scan of its own)
+      ProfScope ps(c, "k_pc_scan", 40.0 * m);
+      hipLaunchKernelGGL(k_pc_scan, dim3(512), dim3(kB), 0, s, m, (const uint64_t*)choff, (const uint64_t*)nch,
+                         (const uint64_t*)p_lo, (const uint64_t*)p_len, (const uint32_t*)psv.p,
+                         (const uint32_t*)(psv.p + m), X.p3[1].col[2], X.p3[2].col[1], count.p);
+      DAS_HIP(hipGetLastError());
+    }
+    if (c.prof) {                                      // (profiling only: the rows read, summed on the device)
+      DBuf<uint64_t> acc(m + 1, s);
+      prof_add_bytes(c, "k_pc_scan", 4.0 * scan_total<uint64_t>(SpanIn<uint64_t>{p_len}, m, acc.p, s));
+    }
+  }
+  {
+    ProfScope ps(c, "k_pc_finish", 28.0 * m);
+    hipLaunchKernelGGL(k_pc_finish, G(m), dim3(kB), 0, s, m, W, (const unsigned long long*)count.p, out->col(2),
+                       out->col(3), out->col(4), out->col(5), out->col(6));
+    DAS_HIP(hipGetLastError());
+  }
+  return out;
+}
+
+}  // namespace das

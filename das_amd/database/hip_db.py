@@ -25,6 +25,7 @@ try:
 except ImportError:                         # pragma: no cover - built with the library
     _hex = None
 from .. import loader as _loader
+from .. import miner as _miner
 from .. import name_search as _name_search
 from ..expression_hasher import ExpressionHasher
 from .db_interface import UNORDERED_LINK_TYPES, WILDCARD, DBInterface
@@ -176,6 +177,7 @@ class HipDB(RelationalDB):
         self._name_stats = {}           # named type id -> (nodes, name bytes, ascii_only), per load
         self._name_dfas = {}            # (pattern, ascii_only) -> NameDFA or None
         self.name_search_stats = {"device": 0, "host": 0}   # get_matched_node_name calls answered by each path
+        self.miner_stats = {"device": 0, "host": 0}         # halo / pattern_counts calls answered by each path
 
     def __repr__(self):
         return "<HipDB>"
@@ -698,6 +700,53 @@ class HipDB(RelationalDB):
             self._name_dfas.clear()
         self._name_dfas[key] = dfa
         return dfa
+
+    # ------------------------------------------ pattern miner (das_amd/miner.py)
+    def _miner_on_device(self):
+        """The device path answers unless DAS_MINER=0, the DB holds stale
+        pattern entries (their bug-for-bug keys are host state) or the index
+        is one shard of several."""
+        return (os.environ.get("DAS_MINER", "1") != "0" and not self._stale
+                and not (self.shard is not None and self.shard[1] > 1))
+
+    def halo(self, seeds, length=2):
+        """SimplePatternMiner.ipynb cell 6 around the seed handles, `length`
+        levels: a miner.Halo (`.links[level]`, `.atoms[level]` id arrays in
+        ascending order, `.universe_size`).  One das_halo_expand call; with
+        DAS_MINER=0 (and for a DB with stale pattern entries) the per-call
+        loop miner.halo_host.  `miner_stats` counts the calls of each path."""
+        if not self._miner_on_device():
+            self.miner_stats["host"] += 1
+            return _miner.halo_host(self, seeds, length)
+        hs = list(dict.fromkeys(seeds))
+        ids = self.ids_of(hs)
+        lt, at = self.ctx.halo_expand(ids[ids >= 0], length)
+        self.miner_stats["device"] += 1
+        return _miner.Halo(self, _miner._Levels(lt), _miner._Levels(at), link_tables=lt)
+
+    def pattern_counts(self, links):
+        """build_patterns' templates of `links` (handles, an id array, or a
+        Halo level, which is read on the device without a host copy) with
+        len(get_links(type, None, template)) of each: a miner.PatternCounts.
+        One das_pattern_counts call; host loop as for `halo`."""
+        if not self._miner_on_device():
+            self.miner_stats["host"] += 1
+            return _miner.pattern_counts_host(self, links)
+        if isinstance(links, _miner.HaloLevel) and links.halo.db is self and links.halo.by_id:
+            src = links.table if links.table is not None else links.ids
+        elif isinstance(links, _miner.HaloLevel):
+            src = self.ids_of(links.handles)
+        elif isinstance(links, np.ndarray) and links.dtype != object:
+            src = links
+        else:
+            ids = self.ids_of([str(h) for h in links])
+            if (ids < 0).any():
+                raise ValueError("pattern_counts: a handle that is not in the knowledge base")
+            src = ids
+        cols = self.ctx.pattern_counts(src)
+        self.miner_stats["device"] += 1
+        count = cols[5].astype(np.uint64) | (cols[6].astype(np.uint64) << np.uint64(32))
+        return _miner.PatternCounts(self, cols[0].copy(), cols[1].copy(), np.ascontiguousarray(cols[2:5].T), count)
 
     def get_matched_node_name(self, node_type: str, substring: str) -> str:
         """redis_mongo_db.py:287-293 (Mongo $regex on names of that type).

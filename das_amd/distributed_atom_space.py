@@ -220,6 +220,26 @@ class DistributedAtomSpace:
     def get_node_name(self, node_handle: str) -> str:
         return self.db.get_node_name(node_handle)
 
+    # -- pattern miner (notebooks/SimplePatternMiner.ipynb cells 6 and 5) ----
+    def halo(self, seeds: List[str], length: int = 2):
+        """The halo walk around the seed handles: a miner.Halo
+        (`.links[level]`, `.atoms[level]`, `.link_handles(level)`,
+        `.universe_size`).  On a HipDB one device call; any other DBInterface
+        runs the notebook's per-call loop (miner.halo_host)."""
+        if hasattr(self.db, "halo"):
+            return self.db.halo(seeds, length)
+        from . import miner
+        return miner.halo_host(self.db, seeds, length)
+
+    def pattern_counts(self, links):
+        """build_patterns' templates of `links` (handles, an id array, or
+        `halo.level(i)`) with their support: a miner.PatternCounts
+        (`.template(i)`, `.handle(i)`, `.pattern(i)`, `.count`, `.as_dict()`)."""
+        if hasattr(self.db, "pattern_counts"):
+            return self.db.pattern_counts(links)
+        from . import miner
+        return miner.pattern_counts_host(self.db, links)
+
     def query(self, query: LogicalExpression, output_format: QueryOutputFormat = QueryOutputFormat.HANDLE) -> str:
         """distributed_atom_space.py:298-321"""
         query_answer = PatternMatchingAnswer()

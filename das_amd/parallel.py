@@ -295,6 +295,16 @@ class ShardedDB(RelationalDB):
     def get_matched_node_name(self, node_type, substring):
         return self.local.get_matched_node_name(node_type, substring)
 
+    def halo(self, seeds, length=2):
+        """miner.halo_host over the sharded per-call API (every rank calls it)."""
+        from . import miner
+        return miner.halo_host(self, seeds, length)
+
+    def pattern_counts(self, links):
+        """miner.pattern_counts_host over the sharded per-call API."""
+        from . import miner
+        return miner.pattern_counts_host(self, links)
+
     def count_atoms(self):
         nodes, links = self.local.count_atoms()
         return (nodes, int(self._allreduce_sum([links])[0]))

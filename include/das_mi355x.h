@@ -241,6 +241,42 @@ int das_match_node_names(das_ctx_t* ctx, uint32_t type_id, const das_name_dfa_t*
  * every name byte is < 0x80 and not '\n' (builds the name heap if need be). */
 int das_node_name_stats(das_ctx_t* ctx, uint32_t type_id, uint64_t* n_nodes, uint64_t* n_bytes, uint32_t* ascii_only);
 
+/* ---- pattern miner (notebooks/SimplePatternMiner.ipynb cells 6 and 5) ----- */
+#define DAS_HALO_MAX_LEVELS 8
+#define DAS_HALO_BLOCK_ENTRIES 1024 /* incoming-list entries one workgroup marks per pass */
+#define DAS_PC_CHUNK_ROWS 1024      /* index rows one wave counts per step of a (1,2)-grounded template */
+/* The halo walk around `seed_ids` (host atom ids, repeats allowed), `levels`
+ * levels deep.  Level 0's frontier is the distinct seeds.  A level finds every
+ * link of arity 2 or 3 whose named type is not in the pattern black list and
+ * that holds a frontier atom at any target position -- the links of
+ * get_links('*', None, t) over the templates [h,*] [*,h] [h,*,*] [*,h,*]
+ * [*,*,h] of every frontier atom h -- and keeps those no earlier level found;
+ * the next frontier is the targets of the kept links that were in no frontier
+ * before.  links_out[l] / atoms_out[l], l < levels: one ordered column each,
+ * the kept link ids and the atoms first reached at level l, ascending (free
+ * each with das_table_free; they work as plan INPUT leaves).  One pass over
+ * the frontier's incoming lists per level, no host round trip per atom; one
+ * read-back of three counts per level.  levels > DAS_HALO_MAX_LEVELS or a
+ * seed id >= n_atoms: DAS_ERR_INVALID; no index: DAS_ERR_NOT_BUILT; an index of
+ * das_build_index_sharded with world > 1: DAS_ERR_UNSUPPORTED -- each before
+ * anything is launched. */
+int das_halo_expand(das_ctx_t* ctx, const uint32_t* seed_ids, uint64_t n_seeds, uint32_t levels,
+                    das_table_t** links_out, das_table_t** atoms_out);
+/* Template support.  The links are column 0 of `links` (e.g. a level of
+ * das_halo_expand) or, when `links` is null, the n host ids `link_ids`.  Each
+ * link of arity 2 gives the templates [T,*,t1] [T,t0,*], each of arity 3
+ * [T,*,t1,t2] [T,t0,*,t2] [T,t0,t1,*] [T,*,*,t2] [T,*,t1,*] [T,t0,*,*]
+ * (build_patterns); a template with a grounded target that is not a node is
+ * dropped, links of other arities give none, equal templates are merged.
+ * *out: one row per template, ordered by (arity, type, targets): columns
+ * arity, type id, t0, t1, t2 (DAS_NONE = wildcard or unused), and the low and
+ * high words of its count = the rows of get_links(T, None, targets): 0 for a
+ * black-listed type; for Similarity / Set under the key the reference builds
+ * (grounded targets sorted by handle after the wildcards).  Errors as
+ * das_halo_expand (a host link id >= n_atoms: DAS_ERR_INVALID). */
+int das_pattern_counts(das_ctx_t* ctx, const das_table_t* links, const uint32_t* link_ids, uint64_t n,
+                       das_table_t** out);
+
 /* ---- query operators ----------------------------------------------------- */
 /* One Link with >= 1 wildcard, evaluated against the pattern index
  * (RedisMongoDB.get_matched_links :235-252 + Link._assign_variables :466-489).
