@@ -42,10 +42,7 @@ std::atomic<int> g_hold{0};                     // > 0: keep every freed block (
 // DAS_ALLOC_TRACE=1: one stderr line per driver allocation (size, host ms)
 // and per out-of-memory fallback, to attribute host gaps in large builds.
 bool alloc_trace() {
-  static const bool on = [] {
-    const char* e = std::getenv("DAS_ALLOC_TRACE");
-    return e && e[0] == '1';
-  }();
+  static const bool on = env_is("DAS_ALLOC_TRACE", '1');
   return on;
 }
 

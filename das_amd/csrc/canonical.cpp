@@ -45,7 +45,7 @@ constexpr uint64_t kNoPos = ~0ull;
 constexpr uint32_t kNoTypeInit = 0xFFFFFFFFu;
 constexpr uint8_t kLeafType = 0, kLeafNode = 1, kLeafOther = 2;
 uint64_t chunk_bytes() {        // DAS_PARSE_CHUNK_BYTES: tests force many small chunks
-  const char* e = std::getenv("DAS_PARSE_CHUNK_BYTES");
+  const char* e = env_str("DAS_PARSE_CHUNK_BYTES");
   const uint64_t v = e ? std::strtoull(e, nullptr, 10) : 0;
   return v ? v : (4ull << 20);
 }
@@ -378,7 +378,7 @@ uint64_t line_of(const Text& t, uint64_t pos) {
 std::unique_ptr<Parsed> parse_canonical(const char* const* texts, const uint64_t* lens, uint32_t n_texts,
                                         unsigned threads) {
   if (!threads) threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  const bool trace = std::getenv("DAS_PARSE_TRACE") != nullptr;
+  const bool trace = env_set("DAS_PARSE_TRACE");
   auto t0 = std::chrono::steady_clock::now();
   auto lap = [&](const char* what) {
     if (!trace) return;

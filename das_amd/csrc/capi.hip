@@ -39,20 +39,14 @@ int fail(das_ctx_t* ctx, int code, const std::string& msg) {
 // DAS_SYNC_CHECK=1: synchronise after every entry point so an asynchronous
 // kernel fault is reported by the call that launched it (debug builds of a run).
 bool sync_check() {
-  static const bool on = [] {
-    const char* e = std::getenv("DAS_SYNC_CHECK");
-    return e && e[0] == '1';
-  }();
+  static const bool on = das::env_is("DAS_SYNC_CHECK", '1');
   return on;
 }
 
 // DAS_HOST_TRACE=1: one stderr line per entry point with its host time (us),
 // to attribute host-side gaps between kernels.
 bool host_trace() {
-  static const bool on = [] {
-    const char* e = std::getenv("DAS_HOST_TRACE");
-    return e && e[0] == '1';
-  }();
+  static const bool on = das::env_is("DAS_HOST_TRACE", '1');
   return on;
 }
 
@@ -330,7 +324,7 @@ struct BuildHold {
   BuildHold() { das::cache_hold(true); }
   ~BuildHold() {
     das::cache_hold(false);
-    const char* k = std::getenv("DAS_BUILD_KEEP_GB");
+    const char* k = das::env_str("DAS_BUILD_KEEP_GB");
     das::cache_trim_to(k ? (size_t)(std::atof(k) * 1e9) : 0);
   }
 };
@@ -1006,7 +1000,7 @@ double now_us() {
 }  // namespace
 
 bool trace_on() {
-  static const bool on = std::getenv("DAS_TRACE") != nullptr;
+  static const bool on = env_set("DAS_TRACE");
   return on;
 }
 void trace_mark(const char* what, const std::string& name) {

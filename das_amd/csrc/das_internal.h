@@ -212,8 +212,7 @@ struct Ctx {
   hipEvent_t take_event() {
     if (ev_pool.empty()) {
       hipEvent_t e;
-      const char* f = std::getenv("DAS_PROF_FENCE");
-      if (f && f[0] == '1') DAS_HIP(hipEventCreate(&e));
+      if (env_is("DAS_PROF_FENCE", '1')) DAS_HIP(hipEventCreate(&e));
       else DAS_HIP(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
       return e;
     }
@@ -252,33 +251,29 @@ struct Ctx {
   hipStream_t side_stream(int i) {
     if (!side[i]) {
       // the batch's other plans (kPlanSide) run beside the lead plan's long
-      // kernels: their queue gets the highest dispatch priority
-      // (DAS_PLAN_PRIO=0: default priority, A/B)
-      // (DAS_CHAIN_PRIO=1: the chains' side streams too, A/B)
+      // kernels: their queue gets the highest dispatch priority (the chains'
+      // side streams keep the default)
       int lo = 0, hi = 0;
-      const char* pp = std::getenv("DAS_PLAN_PRIO");
-      const char* cp = std::getenv("DAS_CHAIN_PRIO");
-      const bool high = i == kPlanSide ? !(pp && pp[0] == '0') : (cp && cp[0] == '1');
-      if (high && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess)
+      if (i == kPlanSide && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess)
         DAS_HIP(hipStreamCreateWithPriority(&side[i], hipStreamNonBlocking, hi));
       else
         DAS_HIP(hipStreamCreateWithFlags(&side[i], hipStreamNonBlocking));
     }
     return side[i];
   }
-  // zeroed grid-chain counter blocks, one per pooled chain of a batch (the
-  // grid kernel leaves its block zero again)
+  // zeroed grid-chain counter blocks, one per read-back level (pub_level():
+  // 0, or 1 inside a PubLevel) for the one-at-a-time chain of that level
+  // (fused_and; the grid kernel leaves its block zero again).  A batch's
+  // pooled chains take fresh counters.
   static constexpr uint32_t kGscBlock = 64;               // words per block (>= the kernel's kGscWords)
+  static constexpr uint32_t kGscBlocks = 2;
   uint32_t* gsc_pool = nullptr;
-  // blocks 0 .. kPubPool-1: a batch's pooled chains; kPubPool + level: the
-  // one-at-a-time chain of each read-back level (fused_and)
-  static constexpr uint32_t kGscBlocks = 18;
-  uint32_t* gsc_block(uint32_t k) {
+  uint32_t* gsc_block(uint32_t level) {
     if (!gsc_pool) {
       DAS_HIP(hipMalloc((void**)&gsc_pool, 4ull * kGscBlock * kGscBlocks));
       DAS_HIP(hipMemset(gsc_pool, 0, 4ull * kGscBlock * kGscBlocks));
     }
-    return gsc_pool + (uint64_t)kGscBlock * (k % kGscBlocks);
+    return gsc_pool + (uint64_t)kGscBlock * (level % kGscBlocks);
   }
   hipEvent_t fence_event(uint32_t i) {
     while (side_ev.size() <= i) {

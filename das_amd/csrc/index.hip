@@ -1040,18 +1040,6 @@ void scatter_partitioned(uint32_t* keys, uint32_t* vals, uint64_t n, uint64_t ke
   if (!n) return;
   DAS_CHECK(n < (1ull << 32), DAS_E_UNSUPPORTED, "scatter_partitioned: more than 2^32 pairs");
   const int bits = std::max(1, bits_for(key_range ? key_range - 1 : 0));
-  // DAS_L2I_BITS=16 (A/B): two LSD passes on the keys' top 16 bits, so the
-  // scatter's windows are key_range / 2^16 slots (L2-sized) instead of / 2^8:
-  // k_scatter_pairs 29 -> 15 ms at 10^9 links, but the second pass costs as
-  // much (build 650-658 vs 649-653 ms, one box), so one pass stays
-  static const int pbits = std::getenv("DAS_L2I_BITS") && std::atoi(std::getenv("DAS_L2I_BITS")) == 16 ? 16 : 8;
-  if (pbits == 16 && bits > 16) {
-    radix_sort_pairs<uint32_t>(keys, vals, n, bits - 16, bits, s);
-    KScope ks("k_scatter_pairs", 12.0 * n);
-    hipLaunchKernelGGL(k_scatter_pairs, G(n), dim3(B), 0, s, (const uint32_t*)keys, (const uint32_t*)vals, n, dst);
-    DAS_HIP(hipGetLastError());
-    return;
-  }
   const int shift = std::max(0, bits - 8);
   const uint32_t tiles = (uint32_t)((n + kSortTile - 1) / kSortTile);
   DBuf<uint32_t> hist((uint64_t)tiles * 256, s), offs((uint64_t)tiles * 256, s), k2(n, s), v2(n, s);
@@ -1250,12 +1238,11 @@ bool sort_by_digest(DigS dig, uint32_t* idx, uint64_t n, DBuf<uint64_t>& key, hi
     }
     // large sorts: the top 40 key bits, then the runs that hold several keys
     // (DAS_DIGEST_PREFIX=0: all 64 bits; =1: the prefix path at any size)
-    const char* pe = std::getenv("DAS_DIGEST_PREFIX");
-    const bool prefix = pe && pe[0] == '1' ? true : n >= (1ull << 22) && !(pe && pe[0] == '0');
+    const char pe = env_char("DAS_DIGEST_PREFIX");
+    const bool prefix = pe == '1' || (n >= (1ull << 22) && pe != '0');
     // (DAS_DIGEST_PREFIX_SHIFT: a shorter prefix, so that most runs need
     // ordering -- tests of the run fix-up)
-    const char* ps = std::getenv("DAS_DIGEST_PREFIX_SHIFT");
-    const int shift = ps ? std::max(2, std::min(56, std::atoi(ps))) : kPrefixShift;
+    const int shift = (int)std::max(2ll, std::min(56ll, env_int("DAS_DIGEST_PREFIX_SHIFT", kPrefixShift)));
     radix_sort_pairs<uint64_t>(key.p, idx, n, prefix ? shift : 0, 64, s);
     if (prefix && !fix_prefix_runs(key.p, idx, n, shift, s))
       radix_sort_pairs<uint64_t>(key.p, idx, n, 0, 64, s);
@@ -1409,12 +1396,9 @@ void build_key_dir(PosIndex& P, Index& idx, hipStream_t s) {
     // 2^28 slots, 1 GiB): a probe's key is then ONE load instead of a binary
     // search over the type's keys (~24 dependent loads at 10^7 keys: config
     // 5's T1 holds ~1.7 10^7 first targets over 1.3 10^8 node ids)
-    // (DAS_KEY_DIR_SPARSE=0: dense ranges only, the round-2/3 rule, for A/B)
-    static const bool sparse = !(std::getenv("DAS_KEY_DIR_SPARSE") && std::getenv("DAS_KEY_DIR_SPARSE")[0] == '0');
-    if (span > 2 * (khi - klo) + 4096 && (!sparse || span > 16 * (khi - klo) || span > (1ull << 28))) {
-      // bucket directory: ~2 keys per bucket (DAS_KEY_BDIR=0: none, A/B)
-      static const bool bd = !(std::getenv("DAS_KEY_BDIR") && std::getenv("DAS_KEY_BDIR")[0] == '0');
-      if (!bd || khi - klo < 64) continue;
+    if (span > 2 * (khi - klo) + 4096 && (span > 16 * (khi - klo) || span > (1ull << 28))) {
+      // bucket directory: ~2 keys per bucket
+      if (khi - klo < 64) continue;
       uint32_t shift = 0;
       while ((span >> shift) > (khi - klo) / 2) ++shift;
       const uint32_t nb = (uint32_t)(((span - 1) >> shift) + 1);
@@ -1430,8 +1414,8 @@ void build_key_dir(PosIndex& P, Index& idx, hipStream_t s) {
       continue;
     }
     // large spans: the rank directory (DAS_KEY_RANK=0: dense, A/B; =1 at any span)
-    const char* rk = std::getenv("DAS_KEY_RANK");
-    if (rk && rk[0] == '1' ? true : span >= (1ull << 20) && !(rk && rk[0] == '0')) {
+    const char rk = env_char("DAS_KEY_RANK");
+    if (rk == '1' || (span >= (1ull << 20) && rk != '0')) {
       const uint64_t nw = (span + 63) / 64;
       uint64_t* rb = dalloc<uint64_t>(idx, nw);
       uint32_t* rp = dalloc<uint32_t>(idx, nw + 1);
@@ -1579,8 +1563,7 @@ namespace {
 }  // namespace
 
 uint64_t host_key_mirror_max() {
-  const char* e = std::getenv("DAS_HOST_KEY_MIRROR");
-  return e ? std::strtoull(e, nullptr, 10) : kHostKeyMirror;
+  return (uint64_t)env_int("DAS_HOST_KEY_MIRROR", (long long)kHostKeyMirror);
 }
 
 void build_index(Ctx& c, const das_atoms_t& a, uint32_t flags, uint32_t shard_rank, uint32_t shard_world) {
@@ -1705,8 +1688,8 @@ void build_index(Ctx& c, const das_atoms_t& a, uint32_t flags, uint32_t shard_ra
   // local2id by a partitioned scatter above 2^22 entries (DAS_L2I_PART=0: the
   // direct 4-byte random scatter, which wrote ~10x its bytes at 10^9 links;
   // =1: partitioned at every size, tests)
-  const char* l2p = std::getenv("DAS_L2I_PART");
-  const bool l2i_part = l2p && l2p[0] == '1' ? nc > 0 : nc >= (1ull << 22) && !(l2p && l2p[0] == '0');
+  const char l2p = env_char("DAS_L2I_PART");
+  const bool l2i_part = l2p == '1' ? nc > 0 : nc >= (1ull << 22) && l2p != '0';
   DBuf<uint32_t> ids(l2i_part ? nc : 0, s);
   if (nc) {
     DBuf<uint8_t> cs(nc, s);
@@ -1750,8 +1733,7 @@ void build_index(Ctx& c, const das_atoms_t& a, uint32_t flags, uint32_t shard_ra
   uint32_t tshift = 0;
   {
     DBuf<uint32_t> perm(n_atoms ? n_atoms : 1, s);
-    const char* dg = std::getenv("DAS_DEGREE_ORDER");
-    const bool degree = !(dg && dg[0] == '0') && ne > 0;
+    const bool degree = !env_is("DAS_DEGREE_ORDER", '0') && ne > 0;
     tshift = degree ? 5u : 0u;
     if (n_atoms) {
       DBuf<uint32_t> cnt, slots;
@@ -2048,7 +2030,7 @@ void build_index(Ctx& c, const das_atoms_t& a, uint32_t flags, uint32_t shard_ra
       for (uint64_t r = 0; r < m; ++r) idx.ctype_range[hk[r]] = CtypeRange{ar, ho[r], ho[r + 1]};
     }
     // P_{a,p}
-    const bool packed = !(std::getenv("DAS_PIDX_PERM") && std::getenv("DAS_PIDX_PERM")[0] == '1') &&
+    const bool packed = !env_is("DAS_PIDX_PERM", '1') &&
                         idx.type_off[ar].size() == a.n_types + 1 && idx.type_off[ar][a.n_types] == R;
     if (ar <= (uint32_t)kMaxPosArity && packed) {
       const RowTable& T = idx.ttab[ar];
@@ -2064,8 +2046,7 @@ void build_index(Ctx& c, const das_atoms_t& a, uint32_t flags, uint32_t shard_ra
         DBuf<uint64_t> pk(R, s);
         // p > 0: from P_{a,0}'s rows (DAS_PIDX_DERIVE=0: each P_{a,p} sorted
         // from the type table on its full key, A/B)
-        const char* dv = std::getenv("DAS_PIDX_DERIVE");
-        const bool derive = p > 0 && (ar == 2 || ar == 3) && !(dv && dv[0] == '0');
+        const bool derive = p > 0 && (ar == 2 || ar == 3) && !env_is("DAS_PIDX_DERIVE", '0');
         const PosIndex& P0 = idx.pidx[ar][0];
         for (uint32_t ty = 0; ty < a.n_types && derive; ++ty) {
           const uint64_t b = to[ty], n = to[ty + 1] - to[ty];
@@ -2104,7 +2085,7 @@ void build_index(Ctx& c, const das_atoms_t& a, uint32_t flags, uint32_t shard_ra
           }
           // a key wider than 64 bits (arity 3): the last field is sorted
           // first on its own (LSD), the rest carry the segment row
-          const bool force_two = std::getenv("DAS_PIDX_TWO") && std::getenv("DAS_PIDX_TWO")[0] == '1';
+          const bool force_two = env_is("DAS_PIDX_TWO", '1');
           const bool two = total > 64 || (nf == 3 && force_two);      // (tests: DAS_PIDX_TWO=1)
           PackKey f{};
           f.n = two ? nf - 1 : nf;

@@ -255,10 +255,10 @@ struct Exec {
   // index join term by term).  DAS_SEMI_MULTI=1 drops the size floor, 0
   // disables the run (tests).
   size_t semi_run(const std::vector<uint32_t>& terms, size_t k, const Rel& acc) const {
-    const char* f = std::getenv("DAS_SEMI_MULTI");
-    if ((f && f[0] == '0') || acc.t.size() != 1) return k;
+    const char f = env_char("DAS_SEMI_MULTI");
+    if (f == '0' || acc.t.size() != 1) return k;
     const Table& a = *acc.t[0];
-    if (a.kind != DAS_TABLE_ORDERED || (!(f && f[0] == '1') && a.nrows <= (1ull << 20))) return k;
+    if (a.kind != DAS_TABLE_ORDERED || (f != '1' && a.nrows <= (1ull << 20))) return k;
     const int32_t v = one_var(terms[k]);
     bool bound = false;
     for (int i = 0; i < a.ncols; ++i) bound |= a.vars[i] == v;
@@ -280,14 +280,14 @@ struct Exec {
   // symmetric, and an empty join empties acc either way), other row order.
   // DAS_REV_IJ=0 off, =1 without the 2^16-row floor (tests).
   TablePtr reverse_ij(int64_t t0, const Rel& acc, const Rel& s) {
-    const char* f = std::getenv("DAS_REV_IJ");
-    if (t0 < 0 || sharded() || (f && f[0] == '0')) return nullptr;
+    const char f = env_char("DAS_REV_IJ");
+    if (t0 < 0 || sharded() || f == '0') return nullptr;
     const das_plan_node_t& a = nd[t0];
     if (a.op != DAS_PLAN_LINK || !a.index_join || a.dedup || acc.t.size() != 1 || s.t.size() != 1) return nullptr;
     const Table& big = *acc.t[0];
     const Table& small = *s.t[0];
     if (small.kind != DAS_TABLE_ORDERED || !small.nrows || 4 * small.nrows > big.nrows) return nullptr;
-    if (!(f && f[0] == '1') && big.nrows < (1ull << 16)) return nullptr;
+    if (f != '1' && big.nrows < (1ull << 16)) return nullptr;
     return index_join(c, small, a.ij);
   }
 
@@ -343,12 +343,8 @@ struct Exec {
   // index-joined Link term k on one of its fresh variables (*v), or k.  The
   // running result must have more than 4096 rows (DAS_SEMI_MULTI as above).
   size_t filt_run(const std::vector<uint32_t>& terms, size_t k, const Table& a, int32_t& v) const {
-    const char* f = std::getenv("DAS_SEMI_MULTI");
-    // DAS_FILT_EXPAND=0 (A/B): the join written out, then filtered by the
-    // key-set intersection (semi_join_multi) instead of the filtered expansion
-    const char* fx = std::getenv("DAS_FILT_EXPAND");
-    if ((f && f[0] == '0') || (fx && fx[0] == '0') || a.kind != DAS_TABLE_ORDERED ||
-        (!(f && f[0] == '1') && a.nrows <= 4096) || k + 1 >= terms.size())
+    const char f = env_char("DAS_SEMI_MULTI");
+    if (f == '0' || a.kind != DAS_TABLE_ORDERED || (f != '1' && a.nrows <= 4096) || k + 1 >= terms.size())
       return k;
     v = one_var(terms[k + 1]);
     if (v < 0) return k;
@@ -554,8 +550,8 @@ struct Views {                          // scans may return index views while pl
     // next: the join kernel runs at ~0.50 of the HBM peak instead of ~0.41,
     // but the bio step is ~4 % slower with the copies, profiles/r3_*).
     // 0: never.
-    const char* f = std::getenv("DAS_SCAN_VIEWS");
-    c.scan_views = f && f[0] == '2' ? 2 : f && f[0] == '0' ? 0 : 1;
+    const char f = env_char("DAS_SCAN_VIEWS");
+    c.scan_views = f == '2' ? 2 : f == '0' ? 0 : 1;
   }
   ~Views() { c.scan_views = 0; }
 };
@@ -649,6 +645,10 @@ PlanOutput plan_execute(Ctx& c, const das_plan_node_t* nodes, uint32_t n, int no
   return output(c, std::move(r));
 }
 
+// a nested plan's launch of this many algorithmic bytes or more waits for the
+// outer plan's kernels (nest_some, below)
+constexpr double kNestGateBytes = 1024.0 * (1 << 20);
+
 std::vector<PlanOutput> plan_execute_many(Ctx& c, const das_plan_node_t* const* nodes, const uint32_t* n,
                                           uint32_t n_plans, int no_overload) {
   DAS_CHECK(c.idx.built, DAS_E_NOT_BUILT, "index not built");
@@ -660,11 +660,10 @@ std::vector<PlanOutput> plan_execute_many(Ctx& c, const das_plan_node_t* const* 
   std::vector<PlanOutput> outs(n_plans);
   std::vector<ChainRunPtr> runs(n_plans);
   std::vector<std::unique_ptr<UnionRun>> uruns(n_plans);
-  const char* f = std::getenv("DAS_DEFER");               // A/B: 0 = every plan in turn
-  const bool defer = !(f && f[0] == '0');
-  const char* fh = std::getenv("DAS_DEFER_HOOK");         // A/B: 0 = chains launched before the other plans
-  const char* sd = std::getenv("DAS_CHAIN_SIDE");         // A/B: 0 = chains on the context's stream
-  const bool side = !(sd && sd[0] == '0');
+  // A/B: 0 = every plan in turn
+  const bool defer = !env_is("DAS_DEFER", '0');
+  // A/B: 0 = chains on the context's stream
+  const bool side = !env_is("DAS_CHAIN_SIDE", '0');
   trace_mark("plans");
   Views v(c);
   // root Ands are the chain candidates; a chain runs on a side stream (its
@@ -673,12 +672,10 @@ std::vector<PlanOutput> plan_execute_many(Ctx& c, const das_plan_node_t* const* 
   std::vector<uint8_t> cand(n_plans, 0), tried(n_plans, 0);
   uint32_t n_cand = 0;
   // (root Ors: their one-launch bitmap union, likewise launched early and
-  // read back last; DAS_DEFER_OR=0 off)
-  const char* fo = std::getenv("DAS_DEFER_OR");
-  const bool defer_or = !(fo && fo[0] == '0');
+  // read back last)
   for (uint32_t i = 0; i < n_plans && defer; ++i) {
     if (n_cand >= kPubPool) break;
-    if (nodes[i][0].op == DAS_PLAN_OR && defer_or && nodes[i][0].nchild >= 2) {
+    if (nodes[i][0].op == DAS_PLAN_OR && nodes[i][0].nchild >= 2) {
       cand[i] = 1;
       ++n_cand;
       continue;
@@ -698,15 +695,11 @@ std::vector<PlanOutput> plan_execute_many(Ctx& c, const das_plan_node_t* const* 
   // 1.443 / 1.486 vs 1.430 / 1.469 ms, hub 0.891 / 0.888 vs 0.894 / 0.892;
   // the lead's cross product holds the CUs and HBM the side plans need,
   // even from a highest-priority queue; profiles/r5_plan_side_ab.txt)
-  const char* ps = std::getenv("DAS_PLAN_SIDE");
-  const bool plan_side = ps && ps[0] == '1' && n_plans - n_cand > 1;
+  const bool plan_side = env_is("DAS_PLAN_SIDE", '1') && n_plans - n_cand > 1;
   // a plan nested in another's long read-back wait (below; DAS_PLAN_NEST=0 off)
-  const char* pn = std::getenv("DAS_PLAN_NEST");
-  const bool nest = !(pn && pn[0] == '0') && n_plans - n_cand > 1;
-  const char* nm = std::getenv("DAS_PLAN_NEST_MIN");             // tests: 0 = at every wait
+  const bool nest = !env_is("DAS_PLAN_NEST", '0') && n_plans - n_cand > 1;
+  const char* nm = env_str("DAS_PLAN_NEST_MIN");             // tests: 0 = at every wait
   const double nest_min = nm ? std::atof(nm) : (double)(128u << 20);
-  const char* ng = std::getenv("DAS_NEST_GATE_MB");               // 0: no gate (A/B)
-  const double gate_min = (ng ? std::atof(ng) : 1024.0) * (1 << 20);
   if ((n_cand && side) || plan_side || nest) {
     // side streams are ordered after the context's stream as it stands when
     // the batch begins (their blocks' last readers), never after this batch's
@@ -797,15 +790,15 @@ std::vector<PlanOutput> plan_execute_many(Ctx& c, const das_plan_node_t* const* 
       PubLevel lv;
       Swap sw{c, c.s};
       c.s = to_side();
-      // its first flood of >= gate_min bytes (bio QUERY_3's 6.6 GB cross
+      // its first flood of >= kNestGateBytes (bio QUERY_3's 6.6 GB cross
       // product) waits for the outer plan's launched kernels: running beside
       // an HBM-bound join it slowed both (a 50 us join took 330 us beside it)
       struct Ungate {
         Ctx& c;
         ~Ungate() { c.gate_s = nullptr; }
       } ug{c};
-      c.gate_s = gate_min > 0 ? sw.old : nullptr;
-      c.gate_min = gate_min;
+      c.gate_s = sw.old;
+      c.gate_min = kNestGateBytes;
       outs[i] = eval_plan(i);
     }
   };
@@ -833,7 +826,7 @@ std::vector<PlanOutput> plan_execute_many(Ctx& c, const das_plan_node_t* const* 
     for (size_t j = cur + 1; j < order.size() && nest; ++j) pending = pending || !done[order[j]];
     return chains_done && !pending;
   };
-  const bool hooked = (n_cand && !(fh && fh[0] == '0')) || nest;
+  const bool hooked = n_cand || nest;
   if (!hooked) launch_all();
   struct Unhook {
     ~Unhook() { set_wait_hook(nullptr); }
@@ -852,7 +845,7 @@ std::vector<PlanOutput> plan_execute_many(Ctx& c, const das_plan_node_t* const* 
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return weight(a) > weight(b); });
   double rest = 0;
   for (size_t j = 1; j < order.size(); ++j) rest += std::max(weight(order[j]), 0.0);
-  const char* sm = std::getenv("DAS_PLAN_SPLIT_MIN");          // tests: 0 = any lead heavier than the rest
+  const char* sm = env_str("DAS_PLAN_SPLIT_MIN");          // tests: 0 = any lead heavier than the rest
   const double split_min = sm ? std::atof(sm) : (double)(64u << 20);
   const bool split = plan_side && weight(order[0]) > std::max(rest, split_min) && weight(order[0]) >= 0;
   for (size_t j = 0; j < order.size(); ++j) {

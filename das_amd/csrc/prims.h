@@ -390,16 +390,6 @@ struct Bounded {
   __device__ __forceinline__ auto operator()(uint64_t i) const -> decltype(in(i)) { return i < n ? in(i) : 0; }
 };
 
-template <typename T, typename In>
-__global__ void k_max_of(In in, uint64_t n, unsigned long long* mx) {
-  uint64_t m = 0;
-  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-    m = (uint64_t)in(i) > m ? (uint64_t)in(i) : m;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) { const uint64_t o = __shfl_xor(m, d, 64); m = o > m ? o : m; }
-  if (__lane_id() == 0 && m) atomicMax(mx, (unsigned long long)m);
-}
-
 constexpr uint64_t kPubMaxTiles = 1024;   // tile sums the last block scans alone (4 block rounds)
 
 // Per-tile sum and max (the multi-level path of scan_total).
@@ -472,54 +462,6 @@ __global__ void __launch_bounds__(kSortBlock) k_radix_hist(const K* keys, uint64
   hist[(uint64_t)threadIdx.x * n_tiles + blockIdx.x] = h[threadIdx.x];
 }
 
-template <typename K, bool kHasVals>
-__global__ void __launch_bounds__(kSortBlock) k_radix_scatter(const K* kin, const uint32_t* vin, K* kout,
-                                                             uint32_t* vout, uint64_t n, int shift,
-                                                             const uint32_t* offs, uint32_t n_tiles) {
-  __shared__ uint32_t s_base[256];
-  __shared__ uint32_t s_cnt[kSortBlock / 64][256];
-  const int tid = threadIdx.x, wave = tid >> 6;
-  s_base[tid] = offs[(uint64_t)tid * n_tiles + blockIdx.x];
-#pragma unroll
-  for (int w = 0; w < kSortBlock / 64; ++w) s_cnt[w][tid] = 0;
-  __syncthreads();
-  const uint64_t base = (uint64_t)blockIdx.x * kSortTile;
-  const uint64_t lt = __lanemask_lt();
-  for (int r = 0; r < kSortItems; ++r) {
-    const uint64_t i = base + (uint64_t)r * kSortBlock + tid;
-    const bool valid = i < n;
-    K k = valid ? kin[i] : (K)0;
-    uint32_t v = 0;
-    if (kHasVals && valid) v = vin[i];
-    const uint32_t d = (uint32_t)(k >> shift) & 255u;
-    uint64_t peers = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const bool bit = (d >> b) & 1u;
-      const uint64_t bb = __ballot(bit);
-      peers &= bit ? bb : ~bb;
-    }
-    const uint32_t rank = __popcll(peers & lt);
-    if (valid && rank == 0) s_cnt[wave][d] = __popcll(peers);
-    __syncthreads();
-    if (valid) {
-      uint32_t pos = s_base[d] + rank;
-      for (int w = 0; w < wave; ++w) pos += s_cnt[w][d];
-      kout[pos] = k;
-      if (kHasVals) vout[pos] = v;
-    }
-    __syncthreads();
-    uint32_t add = 0;
-#pragma unroll
-    for (int w = 0; w < kSortBlock / 64; ++w) {
-      add += s_cnt[w][tid];
-      s_cnt[w][tid] = 0;
-    }
-    s_base[tid] += add;
-    __syncthreads();
-  }
-}
-
 // LDS-staged scatter: the tile's keys are first placed in LDS in digit order
 // (tile-local offsets from the tile's histogram), then written out by
 // consecutive threads, so each digit's run of the tile (~16 keys at 256
@@ -527,8 +469,7 @@ __global__ void __launch_bounds__(kSortBlock) k_radix_scatter(const K* kin, cons
 // 64 buckets per wave store.  Values follow in a second phase through the
 // SAME LDS buffer (each item's tile position and each output slot's global
 // position stay in registers), so a block holds one tile of keys, not keys
-// plus values: twice the resident blocks for 64-bit keys.  Same stable order
-// as k_radix_scatter.
+// plus values: twice the resident blocks for 64-bit keys.  Stable.
 template <typename K, bool kHasVals>
 __global__ void __launch_bounds__(kSortBlock) k_radix_scatter_lds(const K* kin, const uint32_t* vin, K* kout,
                                                                  uint32_t* vout, uint64_t n, int shift,
@@ -792,8 +733,7 @@ void radix_sort_pairs(K* keys, uint32_t* vals, uint64_t n, int begin_bit, int en
   // DAS_ONESWEEP=1: onesweep passes (measured slower at 10^9 keys: each
   // digit's look-back walks earlier tiles one dependent load at a time, so the
   // per-pass histogram kernels stay the default)
-  const char* os_env = std::getenv("DAS_ONESWEEP");
-  const bool onesweep = os_env && os_env[0] == '1';
+  const bool onesweep = env_is("DAS_ONESWEEP", '1');
   if (onesweep && n >= (1ull << 20)) {
     DAS_CHECK(n < (1ull << 32), DAS_E_UNSUPPORTED, "radix sort: more than 2^32 keys");
     const uint32_t tiles = (uint32_t)((n + kSortTile - 1) / kSortTile);
@@ -853,23 +793,15 @@ void radix_sort_pairs(K* keys, uint32_t* vals, uint64_t n, int begin_bit, int en
     }
     DAS_HIP(hipGetLastError());
     exclusive_scan<uint32_t>(hist.p, (uint64_t)tiles * 256, offs.p, s);
-    static const bool lds = !(std::getenv("DAS_SORT_LDS") && std::getenv("DAS_SORT_LDS")[0] == '0');
-    KScope ks(((lds ? "k_radix_scatter_lds<" : "k_radix_scatter<") + tag + (vals ? ",true>" : ",false>")).c_str(),
-              2.0 * kv);
-    if (lds && vals)
+    KScope ks(("k_radix_scatter_lds<" + tag + (vals ? ",true>" : ",false>")).c_str(), 2.0 * kv);
+    if (vals)
       hipLaunchKernelGGL((k_radix_scatter_lds<K, true>), dim3(tiles), dim3(kSortBlock), 0, s, (const K*)ka,
                          (const uint32_t*)va, kb, vb, n, shift, (const uint32_t*)hist.p, (const uint32_t*)offs.p,
                          tiles);
-    else if (lds)
+    else
       hipLaunchKernelGGL((k_radix_scatter_lds<K, false>), dim3(tiles), dim3(kSortBlock), 0, s, (const K*)ka,
                          (const uint32_t*)nullptr, kb, (uint32_t*)nullptr, n, shift, (const uint32_t*)hist.p,
                          (const uint32_t*)offs.p, tiles);
-    else if (vals)
-      hipLaunchKernelGGL((k_radix_scatter<K, true>), dim3(tiles), dim3(kSortBlock), 0, s, (const K*)ka,
-                         (const uint32_t*)va, kb, vb, n, shift, (const uint32_t*)offs.p, tiles);
-    else
-      hipLaunchKernelGGL((k_radix_scatter<K, false>), dim3(tiles), dim3(kSortBlock), 0, s, (const K*)ka,
-                         (const uint32_t*)nullptr, kb, (uint32_t*)nullptr, n, shift, (const uint32_t*)offs.p, tiles);
     DAS_HIP(hipGetLastError());
     std::swap(ka, kb);
     std::swap(va, vb);

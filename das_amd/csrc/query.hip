@@ -20,15 +20,11 @@
 #include <cstring>
 #include <optional>
 #include <string>
+#include <type_traits>
 
 #include "das_internal.h"
 
 namespace das {
-
-__global__ void k_compact_index_q(const uint32_t* flag, const uint32_t* scan, uint64_t n, uint32_t* out) {
-  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-    if (flag[i]) out[scan[i]] = (uint32_t)i;
-}
 
 namespace {
 
@@ -834,7 +830,7 @@ __device__ __forceinline__ void store16(uint32_t* p, u32x4 v) {
   else *reinterpret_cast<u32x4*>(p) = v;
 }
 
-template <int NP, int NB, typename T, int V = 1, bool NT = false>
+template <int NP, int NB, typename T, bool NT = false>
 __device__ __forceinline__ void expand_group(T rs, T re, T pre, uint32_t cnt, uint32_t ex, const uint32_t* pv,
                                              const uint32_t* const* bb, uint32_t* const* po, uint32_t* const* bo,
                                              uint64_t obase, int lane, uint32_t* row, int search) {
@@ -929,7 +925,7 @@ __device__ __forceinline__ void expand_group(T rs, T re, T pre, uint32_t cnt, ui
     // rounds of this iteration that hold outputs (wave-uniform): a group of
     // 64 rows at fan-out ~2 fills 2 of the 4, and the owner searches of an
     // empty round would be a third of the kernel's LDS instructions
-    const int nr = V == 0 ? kXUnroll : (lim - o0) >= (T)(64 * kXUnroll) ? kXUnroll : (int)((lim - o0 + 63) / 64);
+    const int nr = (lim - o0) >= (T)(64 * kXUnroll) ? kXUnroll : (int)((lim - o0 + 63) / 64);
     T o[kXUnroll];
     int l[kXUnroll];
     bool un[kXUnroll];
@@ -1073,7 +1069,7 @@ struct JoinCols {
   int np, nb;
   int search;                    // bit 0: owner lanes by the 6-step ds_bpermute search (DAS_OWNER_SEARCH=1, A/B);
                                  // bit 1: no 16-byte paths (DAS_DJ_VEC=0); bit 2: no quad path
-                                 // (DAS_DJ_VEC=1); bit 3: no run path in the filtered walk (DAS_FILT_RUN=0)
+                                 // (DAS_DJ_VEC=1)
 };
 
 // DAS_OWNER_SEARCH=1: the expansions find each output's owner lane by the
@@ -1081,14 +1077,11 @@ struct JoinCols {
 // DAS_DJ_VEC=0 (bit 1): no 16-byte paths in expand_group; =1 (bit 2): the
 // single-row run path only, no quad path (A/B).
 inline int owner_search_env() {
-  const char* e = std::getenv("DAS_OWNER_SEARCH");
-  const char* v = std::getenv("DAS_DJ_VEC");
-  const char* fr = std::getenv("DAS_FILT_RUN");
-  return (e && e[0] == '1' ? 1 : 0) | (v && v[0] == '0' ? 2 : 0) | (v && v[0] == '1' ? 4 : 0) |
-         (fr && fr[0] == '0' ? 8 : 0);
+  const char vec = env_char("DAS_DJ_VEC");
+  return (env_is("DAS_OWNER_SEARCH", '1') ? 1 : 0) | (vec == '0' ? 2 : 0) | (vec == '1' ? 4 : 0);
 }
 
-template <int NP, int NB, typename T, int V, bool NT = false>
+template <int NP, int NB, typename T, bool NT = false>
 __global__ void __launch_bounds__(B) k_dj_write(const uint32_t* __restrict__ pkey, uint64_t np, uint32_t kmin,
                                                 uint32_t range, const uint2* __restrict__ lc, uint64_t units,
                                                 const uint64_t* __restrict__ unit_off, JoinCols jc,
@@ -1130,7 +1123,7 @@ __global__ void __launch_bounds__(B) k_dj_write(const uint32_t* __restrict__ pke
       const T inc = wave_inclusive_scan(c);
       const T tot = (T)__shfl(inc, 63, 64);
       const T pre = inc - c;                                 // this lane's first output
-      expand_group<NP, NB, T, V, NT>((T)0, tot, pre, e[g].y, e[g].x, pv[g], bb, po, bo, base, lane, row, jc.search);
+      expand_group<NP, NB, T, NT>((T)0, tot, pre, e[g].y, e[g].x, pv[g], bb, po, bo, base, lane, row, jc.search);
       base += tot;
     }
   }
@@ -1200,7 +1193,7 @@ __global__ void __launch_bounds__(B) k_dj_write_bal(const uint32_t* __restrict__
         uint32_t pv[NP > 0 ? NP : 1];
 #pragma unroll
         for (int i = 0; i < NP; ++i) pv[i] = r < np ? pp[i][r] : 0u;
-        expand_group<NP, NB, T, 1, NT>(rs, re, pre, (uint32_t)c, e[g].x, pv, bb, po, bo, gb, lane, row, jc.search);
+        expand_group<NP, NB, T, NT>(rs, re, pre, (uint32_t)c, e[g].x, pv, bb, po, bo, gb, lane, row, jc.search);
       }
     }
   }
@@ -1211,47 +1204,34 @@ void launch_dj_write(unsigned grid, hipStream_t s, const uint32_t* pkey, uint64_
                      const uint2* lc, uint64_t units, const uint64_t* toff, const JoinCols& jc, uint32_t* out,
                      uint64_t cap, uint64_t total, bool balanced, double bytes) {
   const bool wide = total >= (1ull << 32) - (1ull << 16);
-  static const int fixed = std::getenv("DAS_DJ_FIXED") && std::getenv("DAS_DJ_FIXED")[0] == '1';
-  // 16-byte stores nontemporal for outputs of 2^22 rows or more (DAS_DJ_NT=1
-  // always, 0 never); 64-bit-offset and fixed-round launches: plain
-  static const char* nte = std::getenv("DAS_DJ_NT");
-  const bool nt = !wide && (nte && nte[0] == '1' ? true : nte && nte[0] == '0' ? false : total >= (1ull << 22)) &&
-                  (balanced || !fixed);
+  // 16-byte stores nontemporal for outputs of 2^22 rows or more; 64-bit-offset
+  // launches: plain
+  const bool nt = !wide && total >= (1ull << 22);
   // scope names = rocprof's names of the instantiation launched below
   KScope ks((std::string(balanced ? "k_dj_write_bal<" : "k_dj_write<") + std::to_string(NP) + "," +
-             std::to_string(NB) + (wide ? ",u64" : ",u32") + (balanced ? "" : (fixed && !wide) ? ",0" : ",1") +
-             (nt ? ",true>" : ",false>"))
+             std::to_string(NB) + (wide ? ",u64" : ",u32") + (nt ? ",true>" : ",false>"))
                 .c_str(), bytes);
   if (balanced) {
-    // outputs per wave (DAS_BAL_CHUNK, A/B: 512 .. 8192, a multiple of 64)
-    static const uint64_t chunk = [] {
-      const char* e = std::getenv("DAS_BAL_CHUNK");
-      const uint64_t v = e ? std::strtoull(e, nullptr, 10) : kBalChunk;
-      return v >= 64 && v <= 8192 && v % 64 == 0 ? v : kBalChunk;
-    }();
-    const unsigned g = grid_for((total + chunk - 1) / chunk, B / 64, 65535u * 4u);
+    const unsigned g = grid_for((total + kBalChunk - 1) / kBalChunk, B / 64, 65535u * 4u);
     if (wide)
       hipLaunchKernelGGL((k_dj_write_bal<NP, NB, uint64_t>), dim3(g), dim3(B), 0, s, pkey, np, kmin, range, lc, units,
-                         toff, jc, out, cap, total, chunk);
+                         toff, jc, out, cap, total, kBalChunk);
     else if (nt)
       hipLaunchKernelGGL((k_dj_write_bal<NP, NB, uint32_t, true>), dim3(g), dim3(B), 0, s, pkey, np, kmin, range, lc,
-                         units, toff, jc, out, cap, total, chunk);
+                         units, toff, jc, out, cap, total, kBalChunk);
     else
       hipLaunchKernelGGL((k_dj_write_bal<NP, NB, uint32_t, false>), dim3(g), dim3(B), 0, s, pkey, np, kmin, range, lc,
-                         units, toff, jc, out, cap, total, chunk);
+                         units, toff, jc, out, cap, total, kBalChunk);
     return;
   }
   if (wide) {
-    hipLaunchKernelGGL((k_dj_write<NP, NB, uint64_t, 1>), dim3(grid), dim3(B), 0, s, pkey, np, kmin, range, lc, units,
-                       toff, jc, out, cap);
-  } else if (fixed) {
-    hipLaunchKernelGGL((k_dj_write<NP, NB, uint32_t, 0>), dim3(grid), dim3(B), 0, s, pkey, np, kmin, range, lc, units,
+    hipLaunchKernelGGL((k_dj_write<NP, NB, uint64_t>), dim3(grid), dim3(B), 0, s, pkey, np, kmin, range, lc, units,
                        toff, jc, out, cap);
   } else if (nt) {
-    hipLaunchKernelGGL((k_dj_write<NP, NB, uint32_t, 1, true>), dim3(grid), dim3(B), 0, s, pkey, np, kmin, range, lc,
+    hipLaunchKernelGGL((k_dj_write<NP, NB, uint32_t, true>), dim3(grid), dim3(B), 0, s, pkey, np, kmin, range, lc,
                        units, toff, jc, out, cap);
   } else {
-    hipLaunchKernelGGL((k_dj_write<NP, NB, uint32_t, 1, false>), dim3(grid), dim3(B), 0, s, pkey, np, kmin, range, lc,
+    hipLaunchKernelGGL((k_dj_write<NP, NB, uint32_t, false>), dim3(grid), dim3(B), 0, s, pkey, np, kmin, range, lc,
                        units, toff, jc, out, cap);
   }
 }
@@ -1315,9 +1295,8 @@ struct FiltKey {
 // MODE 3 (MODE 2 staged): a chunk's kept outputs are collected in its wave's
 // LDS rows (stage: NPC + NBC columns of CH) and leave as 16-byte stores to
 // the chunk's scratch slots (+ its count, for k_chunk_compact) instead of
-// each lane's scattered 4-byte stores; with `kept` set, at a place reserved
-// by ONE atomic per chunk instead (no scratch, no compaction; unsorted).
-template <int MODE, int NPC, int NBC, int CH, int XU>
+// each lane's scattered 4-byte stores.
+template <int MODE, int NPC, int NBC, int CH>
 __device__ __forceinline__ void dj_filt_body(const uint32_t* __restrict__ pkey, uint64_t np, uint32_t kmin,
                                              uint32_t range, const uint2* __restrict__ lc, uint64_t units,
                                              const uint64_t* __restrict__ unit_off, uint64_t total, FiltKey fk,
@@ -1325,7 +1304,6 @@ __device__ __forceinline__ void dj_filt_body(const uint32_t* __restrict__ pkey, 
                                              const uint32_t* __restrict__ coff, const JoinCols& jc,
                                              uint32_t* __restrict__ out, uint64_t cap, uint64_t wlo, uint64_t whi,
                                              uint32_t* row, uint32_t* stage = nullptr,
-                                             unsigned long long* kept = nullptr,
                                              const uint32_t* __restrict__ cunit = nullptr) {
   const uint64_t waves = (uint64_t)gridDim.x * (B / 64);
   const int lane = __lane_id();
@@ -1403,7 +1381,7 @@ __device__ __forceinline__ void dj_filt_body(const uint32_t* __restrict__ pkey, 
         // load and 4 bitmap words, and the kept ones leave compacted by a
         // wave prefix sum -- instead of 4 rounds of owner lanes, 4-byte
         // gathers and ballots (DAS_DJ_VEC=0: off)
-        const bool runs = MODE >= 2 && ncb == 1 && fk.bcol == 0 && !(jc.search & 10) && (re - rs) > 256u;
+        const bool runs = MODE >= 2 && ncb == 1 && fk.bcol == 0 && !(jc.search & 2) && (re - rs) > 256u;
         for (uint32_t o0 = rs; o0 < re;) {
           if (runs && re - o0 >= 256u) {
             const uint64_t m0 = __ballot(pre <= o0);
@@ -1450,12 +1428,12 @@ __device__ __forceinline__ void dj_filt_body(const uint32_t* __restrict__ pkey, 
               continue;
             }
           }
-          const int nr = (re - o0) >= 64u * XU ? XU : (int)((re - o0 + 63) / 64);
-          uint32_t o[XU], br[XU];
-          int ll[XU];
-          bool un[XU];
+          const int nr = (re - o0) >= 64u * kXUnroll ? kXUnroll : (int)((re - o0 + 63) / 64);
+          uint32_t o[kXUnroll], br[kXUnroll];
+          int ll[kXUnroll];
+          bool un[kXUnroll];
 #pragma unroll
-          for (int q = 0; q < XU; ++q) {
+          for (int q = 0; q < kXUnroll; ++q) {
             o[q] = o0 + (uint32_t)(q * 64 + lane);
             ll[q] = 0;
             un[q] = false;
@@ -1477,44 +1455,44 @@ __device__ __forceinline__ void dj_filt_body(const uint32_t* __restrict__ pkey, 
             br[q] = lane_get(e[g].x, l) + (o[q] - (uint32_t)__shfl(pre, l, 64));
           }
           if (MODE == 0) {
-            uint32_t v[XU];
+            uint32_t v[kXUnroll];
 #pragma unroll
-            for (int q = 0; q < XU; ++q) v[q] = (q < nr && o[q] < re) ? fk.col[br[q]] - fk.lo : 0xFFFFFFFFu;
-            uint32_t wd[XU];
+            for (int q = 0; q < kXUnroll; ++q) v[q] = (q < nr && o[q] < re) ? fk.col[br[q]] - fk.lo : 0xFFFFFFFFu;
+            uint32_t wd[kXUnroll];
 #pragma unroll
-            for (int q = 0; q < XU; ++q) wd[q] = v[q] < fk.range ? fk.bits[v[q] >> 5] : 0u;
+            for (int q = 0; q < kXUnroll; ++q) wd[q] = v[q] < fk.range ? fk.bits[v[q] >> 5] : 0u;
 #pragma unroll
-            for (int q = 0; q < XU; ++q) {
+            for (int q = 0; q < kXUnroll; ++q) {
               if (q >= nr) continue;
               const bool f = v[q] < fk.range && ((wd[q] >> (v[q] & 31)) & 1u);
               if (o[q] < re) fl[gb + o[q]] = f ? 1 : 0;
               run += (uint32_t)__popcll(__ballot(f));
             }
           } else {
-            bool f[XU];
-            uint32_t v[XU];
+            bool f[kXUnroll];
+            uint32_t v[kXUnroll];
             if constexpr (MODE == 1) {
 #pragma unroll
-              for (int q = 0; q < XU; ++q) f[q] = q < nr && o[q] < re && fl[gb + o[q]] != 0;
+              for (int q = 0; q < kXUnroll; ++q) f[q] = q < nr && o[q] < re && fl[gb + o[q]] != 0;
             } else {
 #pragma unroll
-              for (int q = 0; q < XU; ++q) v[q] = (q < nr && o[q] < re) ? fk.col[br[q]] - fk.lo : 0xFFFFFFFFu;
-              uint32_t wd[XU];
+              for (int q = 0; q < kXUnroll; ++q) v[q] = (q < nr && o[q] < re) ? fk.col[br[q]] - fk.lo : 0xFFFFFFFFu;
+              uint32_t wd[kXUnroll];
 #pragma unroll
-              for (int q = 0; q < XU; ++q) wd[q] = v[q] < fk.range ? fk.bits[v[q] >> 5] : 0u;
+              for (int q = 0; q < kXUnroll; ++q) wd[q] = v[q] < fk.range ? fk.bits[v[q] >> 5] : 0u;
 #pragma unroll
-              for (int q = 0; q < XU; ++q) f[q] = v[q] < fk.range && ((wd[q] >> (v[q] & 31)) & 1u);
+              for (int q = 0; q < kXUnroll; ++q) f[q] = v[q] < fk.range && ((wd[q] >> (v[q] & 31)) & 1u);
             }
             // build columns of the kept outputs (MODE 2: the filtered column
             // is the value just tested, no second load)
-            uint32_t bv[XU][4];
+            uint32_t bv[kXUnroll][4];
 #pragma unroll
-            for (int q = 0; q < XU; ++q)
+            for (int q = 0; q < kXUnroll; ++q)
 #pragma unroll
               for (int i = 0; i < 4; ++i)
                 bv[q][i] = (i < ncb && f[q]) ? (MODE >= 2 && i == fk.bcol ? v[q] + fk.lo : bp[i][br[q]]) : 0u;
 #pragma unroll
-            for (int q = 0; q < XU; ++q) {
+            for (int q = 0; q < kXUnroll; ++q) {
               if (q >= nr) continue;
               const uint64_t m = __ballot(f[q]);
               const uint64_t pos = obase + run + __popcll(m & lt);
@@ -1539,47 +1517,34 @@ __device__ __forceinline__ void dj_filt_body(const uint32_t* __restrict__ pkey, 
               }
             }
           }
-          o0 += 64u * XU;
+          o0 += 64u * kXUnroll;
         }
       }
     }
     if constexpr (MODE == 3) {
-      // the chunk's kept rows, LDS -> the chunk's slots (or a reserved place)
-      // of the output: a head of <= 3 rows aligns the destination, 16-byte
-      // stores, a tail of <= 3
-      if (!kept && lane == 0) ccnt[w] = run;
+      // the chunk's kept rows, LDS -> the chunk's slots of the scratch (`cap`
+      // is a multiple of 4, so every column's slots are 16-byte aligned):
+      // 16-byte stores, a tail of <= 3
+      if (lane == 0) ccnt[w] = run;
       if (run) {
         // (LDS writes and reads of one wave stay in program order; the
         // barrier keeps the compiler from moving them across each other)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        unsigned long long b = 0;
-        if (kept && lane == 0) b = atomicAdd(kept, (unsigned long long)run);
-        if (!kept) b = (unsigned long long)(w - wlo) * CH;
+        const unsigned long long b = (unsigned long long)(w - wlo) * CH;
         const uint64_t base = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), 0) << 32) |
                               (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, 0);
-        const uint32_t h = (4u - (uint32_t)(base & 3u)) & 3u;
-        const uint32_t head = h < run ? h : run;
-        const uint32_t nq = (run - head) / 4u;
-        const uint32_t t0 = head + 4u * nq;
+        const uint32_t nq = run / 4u;
+        const uint32_t t0 = 4u * nq;
         for (int k = 0; k < ncp + ncb; ++k) {
           const uint32_t* sc = stage + (uint64_t)k * CH;
           const int col = k < ncp ? jc.po[k] : jc.bo[k - ncp];
           uint32_t* dc = out + (uint64_t)col * cap + base;
-          if ((uint32_t)lane < head) dc[lane] = sc[lane];
-          if (head == 0) {
-            // chunk slots (CH-aligned, the default): the LDS quads are 16-byte
-            // aligned too -- one conflict-free ds_read_b128 per lane instead
-            // of four dword reads 16 bytes apart (4-way bank conflicts)
-            for (uint32_t q = (uint32_t)lane; q < nq; q += 64u)
-              store16<true>(dc + 4u * q, *reinterpret_cast<const u32x4*>(sc + 4u * q));
-          } else {
-            for (uint32_t q = (uint32_t)lane; q < nq; q += 64u) {
-              const uint32_t j = head + 4u * q;
-              store16<true>(dc + j, u32x4{sc[j], sc[j + 1], sc[j + 2], sc[j + 3]});
-            }
-          }
+          // the LDS quads are 16-byte aligned too: one conflict-free
+          // ds_read_b128 per lane instead of four dword reads 16 bytes apart
+          for (uint32_t q = (uint32_t)lane; q < nq; q += 64u)
+            store16<true>(dc + 4u * q, *reinterpret_cast<const u32x4*>(sc + 4u * q));
           if (t0 + (uint32_t)lane < run) dc[t0 + lane] = sc[t0 + lane];
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1592,7 +1557,7 @@ __device__ __forceinline__ void dj_filt_body(const uint32_t* __restrict__ pkey, 
   }
 }
 
-template <int MODE, int NPC = -1, int NBC = -1, int CH = (int)kBalChunk, int XU = kXUnroll>
+template <int MODE, int NPC, int NBC>
 __global__ void __launch_bounds__(B) k_dj_filt(const uint32_t* __restrict__ pkey, uint64_t np, uint32_t kmin,
                                                uint32_t range, const uint2* __restrict__ lc, uint64_t units,
                                                const uint64_t* __restrict__ unit_off, uint64_t total, FiltKey fk,
@@ -1601,37 +1566,37 @@ __global__ void __launch_bounds__(B) k_dj_filt(const uint32_t* __restrict__ pkey
                                                uint32_t* __restrict__ out, uint64_t cap, uint64_t wlo,
                                                uint64_t whi) {
   __shared__ uint32_t s_row[B / 64][64];                    // owner_of_round's row per wave
-  dj_filt_body<MODE, NPC, NBC, CH, XU>(pkey, np, kmin, range, lc, units, unit_off, total, fk, fl, ccnt, coff, jc, out,
+  dj_filt_body<MODE, NPC, NBC, (int)kBalChunk>(pkey, np, kmin, range, lc, units, unit_off, total, fk, fl, ccnt, coff, jc, out,
                                        cap, wlo, whi, s_row[threadIdx.x >> 6]);
 }
 
-// MODE 3: chunks of CH outputs, each wave's kept rows staged in LDS, then
-// written to the chunk's slots [(w - wlo) CH, + ccnt[w]) of `out` (a scratch
-// for k_chunk_compact), or -- kept non-null -- at a place reserved by one
-// atomic on *kept (A/B: DAS_FILT_STAGED=atomic)
-template <int NPC, int NBC, int CH>
+// MODE 3: chunks of kStageChunk outputs, each wave's kept rows staged in LDS,
+// then written to the chunk's slots [(w - wlo) kStageChunk, + ccnt[w]) of
+// `out` (a scratch for k_chunk_compact)
+constexpr int kStageChunk = 512;
+template <int NPC, int NBC>
 __global__ void __launch_bounds__(B) k_dj_filt_staged(const uint32_t* __restrict__ pkey, uint64_t np, uint32_t kmin,
                                                       uint32_t range, const uint2* __restrict__ lc, uint64_t units,
                                                       const uint64_t* __restrict__ unit_off, uint64_t total,
                                                       FiltKey fk, JoinCols jc, uint32_t* __restrict__ out,
                                                       uint64_t cap, uint64_t wlo, uint64_t whi,
-                                                      uint32_t* __restrict__ ccnt, unsigned long long* __restrict__ kept,
+                                                      uint32_t* __restrict__ ccnt,
                                                       const uint32_t* __restrict__ cunit) {
   __shared__ uint32_t s_row[B / 64][64];
-  __shared__ __attribute__((aligned(16))) uint32_t s_stage[B / 64][(NPC + NBC) * CH];
-  dj_filt_body<3, NPC, NBC, CH, kXUnroll>(pkey, np, kmin, range, lc, units, unit_off, total, fk, nullptr, ccnt,
-                                          nullptr, jc, out, cap, wlo, whi, s_row[threadIdx.x >> 6],
-                                          s_stage[threadIdx.x >> 6], kept, cunit);
+  __shared__ __attribute__((aligned(16))) uint32_t s_stage[B / 64][(NPC + NBC) * kStageChunk];
+  dj_filt_body<3, NPC, NBC, kStageChunk>(pkey, np, kmin, range, lc, units, unit_off, total, fk, nullptr, ccnt,
+                                         nullptr, jc, out, cap, wlo, whi, s_row[threadIdx.x >> 6],
+                                         s_stage[threadIdx.x >> 6], cunit);
 }
 
-// For every CH-output chunk, the unit holding its first output (the last unit
-// u with unit_off[u] <= w CH), one thread per chunk: the walk's per-chunk
-// search (4 dependent rounds inside its latency chain) becomes one load
-template <int CH>
+// For every chunk of the staged walk, the unit holding its first output (the
+// last unit u with unit_off[u] <= w kStageChunk), one thread per chunk: the
+// walk's per-chunk search (4 dependent rounds inside its latency chain)
+// becomes one load
 __global__ void __launch_bounds__(B) k_chunk_units(const uint64_t* __restrict__ unit_off, uint64_t units,
                                                    uint64_t chunks, uint32_t* __restrict__ cunit) {
   for (uint64_t w = blockIdx.x * (uint64_t)B + threadIdx.x; w < chunks; w += (uint64_t)gridDim.x * B) {
-    const uint64_t ob = w * CH;
+    const uint64_t ob = w * (uint64_t)kStageChunk;
     uint64_t lo = 0, hi = units;
     while (hi - lo > 1) {
       const uint64_t mid = (lo + hi) >> 1;
@@ -1679,184 +1644,6 @@ __global__ void __launch_bounds__(B) k_chunk_compact(const uint32_t* __restrict_
       }
       if (t0 + lane < n) dc[t0 + lane] = sc[t0 + lane];
     }
-  }
-}
-
-// Single pass of the filtered expansion.  A block takes kFuseChunks 1024-output
-// chunks per wave; pass A tests every output's build value against the key
-// bitmap (flag bytes in LDS, kept count per chunk), ONE atomic per block
-// reserves the block's kept outputs at the end of the output, pass B re-walks
-// the chunks (probe rows, owner prefixes and build rows are cache-resident now)
-// and writes the kept outputs in chunk order.  Blocks land in completion
-// order, so the output is not sorted; no flag array goes through HBM and the
-// virtual outputs are walked from HBM once.
-constexpr int kFuseChunks = 4;
-template <int NPC = -1, int NBC = -1>
-__global__ void __launch_bounds__(B) k_dj_filt_fused(const uint32_t* __restrict__ pkey, uint64_t np, uint32_t kmin,
-                                                     uint32_t range, const uint2* __restrict__ lc, uint64_t units,
-                                                     const uint64_t* __restrict__ unit_off, uint64_t total,
-                                                     FiltKey fk, JoinCols jc, uint32_t* __restrict__ out,
-                                                     uint64_t cap, unsigned long long* __restrict__ kept) {
-  __shared__ uint8_t sflag[B / 64][kFuseChunks][kBalChunk];
-  __shared__ uint32_t s_cnt[B / 64];
-  __shared__ unsigned long long s_base;
-  const int lane = __lane_id();
-  const int wv = threadIdx.x >> 6;
-  const uint64_t lt = __lanemask_lt();
-  const uint64_t chunks = (total + kBalChunk - 1) / kBalChunk;
-  const uint64_t per_block = (uint64_t)(B / 64) * kFuseChunks;
-  const int ncp = NPC >= 0 ? NPC : jc.np, ncb = NBC >= 0 ? NBC : jc.nb;
-  const uint32_t* pp[4];
-  const uint32_t* bp[4];
-  uint32_t* po[4];
-  uint32_t* bo[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    pp[i] = i < ncp ? jc.p[i] : nullptr;
-    bp[i] = i < ncb ? jc.b[i] : nullptr;
-    po[i] = i < ncp ? out + (uint64_t)jc.po[i] * cap : nullptr;
-    bo[i] = i < ncb ? out + (uint64_t)jc.bo[i] * cap : nullptr;
-  }
-  // block-uniform trip count: every wave reaches the barriers
-  for (uint64_t it = blockIdx.x; it * per_block < chunks; it += gridDim.x) {
-    uint32_t cnt[kFuseChunks];
-    uint64_t cbase[kFuseChunks];
-    for (int pass = 0; pass < 2; ++pass) {
-      if (pass == 1) {
-        uint32_t tot = 0;
-#pragma unroll
-        for (int k = 0; k < kFuseChunks; ++k) tot += cnt[k];
-        if (lane == 0) s_cnt[wv] = tot;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-          uint32_t all = 0;
-          for (int w = 0; w < B / 64; ++w) all += s_cnt[w];
-          s_base = all ? atomicAdd(kept, (unsigned long long)all) : 0ull;
-        }
-        __syncthreads();
-        uint64_t o0 = s_base;
-        for (int w = 0; w < wv; ++w) o0 += s_cnt[w];
-#pragma unroll
-        for (int k = 0; k < kFuseChunks; ++k) {
-          cbase[k] = o0;
-          o0 += cnt[k];
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < kFuseChunks; ++k) {
-        const uint64_t w = it * per_block + (uint64_t)wv * kFuseChunks + k;
-        if (pass == 0) cnt[k] = 0;
-        if (w >= chunks || (pass == 1 && !cnt[k])) continue;
-        uint8_t* fl = sflag[wv][k];
-        const uint64_t ob = w * kBalChunk;
-        const uint64_t oe = ob + kBalChunk < total ? ob + kBalChunk : total;
-        uint64_t ulo = 0, uhi = units;                 // last unit with unit_off[u] <= ob
-        while (uhi - ulo > 1) {
-          const uint64_t step = (uhi - ulo + 63) / 64;
-          const uint64_t idx = ulo + (uint64_t)lane * step;
-          const bool ok = idx < uhi && unit_off[idx] <= ob;
-          const uint64_t m = __ballot(ok);
-          const uint64_t nlo = ulo + (uint64_t)(63 - __clzll((long long)m)) * step;
-          uhi = nlo + step < uhi ? nlo + step : uhi;
-          ulo = nlo;
-        }
-        uint32_t run = 0;
-        for (uint64_t u = ulo; u < units; ++u) {
-          uint64_t base = unit_off[u];
-          if (base >= oe) break;
-          const uint64_t r0 = u * kXRows;
-          uint2 e[kXGroups];
-#pragma unroll
-          for (int g = 0; g < kXGroups; ++g) {
-            const uint64_t r = r0 + g * 64 + lane;
-            const uint32_t d = r < np ? pkey[r] - kmin : 0xFFFFFFFFu;
-            e[g] = d < range ? lc[d] : make_uint2(0u, 0u);
-          }
-#pragma unroll
-          for (int g = 0; g < kXGroups; ++g) {
-            const uint32_t c = e[g].y;
-            const uint32_t inc = wave_inclusive_scan(c);
-            const uint32_t tot = (uint32_t)__shfl(inc, 63, 64);
-            const uint32_t pre = inc - c;
-            const uint64_t gb = base, ge = base + tot;
-            base = ge;
-            if (ge <= ob || gb >= oe) continue;
-            const uint32_t rs = (uint32_t)((ob > gb ? ob : gb) - gb), re = (uint32_t)((oe < ge ? oe : ge) - gb);
-            const uint64_t r = r0 + g * 64 + lane;
-            uint32_t pv[4] = {0u, 0u, 0u, 0u};
-            if (pass == 1) {
-#pragma unroll
-              for (int i = 0; i < 4; ++i)
-                if (i < ncp) pv[i] = r < np ? pp[i][r] : 0u;
-            }
-            for (uint32_t o0 = rs; o0 < re; o0 += 64 * kXUnroll) {
-              const int nr = (re - o0) >= 64u * kXUnroll ? kXUnroll : (int)((re - o0 + 63) / 64);
-              uint32_t o[kXUnroll], br[kXUnroll];
-              int ll[kXUnroll];
-#pragma unroll
-              for (int q = 0; q < kXUnroll; ++q) {
-                o[q] = o0 + (uint32_t)(q * 64 + lane);
-                ll[q] = 0;
-                br[q] = 0;
-                if (q >= nr) continue;
-                int l = 0;                             // owner: max lane with pre <= o
-#pragma unroll
-                for (int st = 32; st >= 1; st >>= 1) {
-                  const uint32_t pl = (uint32_t)__shfl(pre, l + st, 64);
-                  if (l + st < 64 && pl <= o[q]) l += st;
-                }
-                ll[q] = l;
-                br[q] = lane_get(e[g].x, l) + (o[q] - (uint32_t)__shfl(pre, l, 64));
-              }
-              if (pass == 0) {
-                uint32_t v[kXUnroll];
-#pragma unroll
-                for (int q = 0; q < kXUnroll; ++q) v[q] = (q < nr && o[q] < re) ? fk.col[br[q]] - fk.lo : 0xFFFFFFFFu;
-                uint32_t wd[kXUnroll];
-#pragma unroll
-                for (int q = 0; q < kXUnroll; ++q) wd[q] = v[q] < fk.range ? fk.bits[v[q] >> 5] : 0u;
-#pragma unroll
-                for (int q = 0; q < kXUnroll; ++q) {
-                  if (q >= nr) continue;
-                  const bool f = v[q] < fk.range && ((wd[q] >> (v[q] & 31)) & 1u);
-                  if (o[q] < re) fl[gb + o[q] - ob] = f ? 1 : 0;
-                  run += (uint32_t)__popcll(__ballot(f));
-                }
-              } else {
-                bool f[kXUnroll];
-#pragma unroll
-                for (int q = 0; q < kXUnroll; ++q) f[q] = q < nr && o[q] < re && fl[gb + o[q] - ob] != 0;
-                uint32_t bv[kXUnroll][4];
-#pragma unroll
-                for (int q = 0; q < kXUnroll; ++q)
-#pragma unroll
-                  for (int i = 0; i < 4; ++i) bv[q][i] = (i < ncb && f[q]) ? bp[i][br[q]] : 0u;
-#pragma unroll
-                for (int q = 0; q < kXUnroll; ++q) {
-                  if (q >= nr) continue;
-                  const uint64_t m = __ballot(f[q]);
-                  const uint64_t pos = cbase[k] + run + __popcll(m & lt);
-                  run += (uint32_t)__popcll(m);
-#pragma unroll
-                  for (int i = 0; i < 4; ++i) {
-                    if (i >= ncp) break;
-                    const uint32_t x = lane_get(pv[i], ll[q]);
-                    if (f[q]) po[i][pos] = x;
-                  }
-                  if (f[q]) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                      if (i < ncb) bo[i][pos] = bv[q][i];
-                  }
-                }
-              }
-            }
-          }
-        }
-        if (pass == 0) cnt[k] = run;
-      }
-    }
-    __syncthreads();                                   // LDS flags and counts reused next iteration
   }
 }
 
@@ -2075,8 +1862,8 @@ std::unique_ptr<Table> compact_pred(Ctx& c, const Table& a, Pred pred, const cha
                                     double pred_bytes = 4.0, const uint32_t* guard = nullptr) {
   const uint64_t n = a.nrows;
   if (!n) return gather_table(c, a, nullptr, 0);
-  const char* sg = std::getenv("DAS_SMALL_GUARD");        // A/B: 0 = read the guard first
-  const bool fused_guard = !(sg && sg[0] == '0');
+  // A/B: 0 = read the guard first
+  const bool fused_guard = !env_is("DAS_SMALL_GUARD", '0');
   if (guard && (n >= (1ull << 31) || (n <= kSmallScan && !fused_guard))) {   // read it first
     if (read_u32(guard, c.s)) return nullptr;
     guard = nullptr;
@@ -2650,13 +2437,12 @@ std::unique_ptr<Table> dj_expand(Ctx& c, const Table& P, const uint32_t* pkey, u
     // a view's payload columns are read cold by the expansion: warm them here
     const uint32_t* w[2] = {nullptr, nullptr};
     int nw = 0;
-    const char* wf = std::getenv("DAS_DJ_WARM");           // A/B: 0 = no warming
-    if (P.view && !(wf && wf[0] == '0'))
+    // A/B: 0 = no warming
+    if (P.view && !env_is("DAS_DJ_WARM", '0'))
       for (int i = 0; i < jc.np && nw < 2; ++i)
         if (jc.p[i] != pkey) w[nw++] = jc.p[i];
     // (DAS_COUNT_PUB=0: the count and the scan as two launches, A/B)
-    const char* cpe = std::getenv("DAS_COUNT_PUB");
-    fused = units <= kCountPubUnits && !(cpe && cpe[0] == '0');
+    fused = units <= kCountPubUnits && !env_is("DAS_COUNT_PUB", '0');
     ProfScope ps(c, fused ? "k_dj_count_pub" : "k_dj_count", 4.0 * P.nrows);
     if (fused) {
       ScanCtr& ct = scan_ctr(c.s);
@@ -2683,7 +2469,7 @@ std::unique_ptr<Table> dj_expand(Ctx& c, const Table& P, const uint32_t* pkey, u
   const uint64_t total = tm[0];
   // a unit owning far more outputs than a wave should expand alone (hub
   // keys) -> output-balanced expansion
-  const char* fb = std::getenv("DAS_DJ_BALANCED");        // tests: force either expansion
+  const char* fb = env_str("DAS_DJ_BALANCED");        // tests: force either expansion
   // ... and so should a probe with a high fan-out everywhere (an index join
   // of 10^5 anchors x 10^2 links each): its few hundred waves would each
   // expand thousands of outputs while most of the chip idles
@@ -2771,7 +2557,7 @@ std::unique_ptr<Table> direct_join(Ctx& c, const Table& P, const Table& Q, int32
     }
     return dj_expand(c, P, pkey, kmin, range, lcp, jc, nu, uni.data(), 4.0 * Q.nrows * Q.ncols);
   };
-  const char* bm = std::getenv("DAS_DJ_BUILD");   // A/B, tests: "dense" never, "sparse" whenever it fits
+  const char* bm = env_str("DAS_DJ_BUILD");   // A/B, tests: "dense" never, "sparse" whenever it fits
   const bool sparse = range < (1ull << 31) &&
       (bm && !std::strcmp(bm, "sparse") ? true
        : bm && !std::strcmp(bm, "dense") ? false : range > 16 * Q.nrows && range >= (1ull << 16) && Q.nrows <= (1ull << 18));
@@ -2782,10 +2568,9 @@ std::unique_ptr<Table> direct_join(Ctx& c, const Table& P, const Table& Q, int32
     // writes instead of a 112 MB fill per bio QUERY_3 join; DAS_ZLC=0: a
     // fresh array filled per join, A/B)
     const bool srt = Q.sorted_col == qk;
-    const char* zf = std::getenv("DAS_ZLC");
     // the context keeps the zeroed array for ranges up to 2^26 slots (512 MB);
     // a wider range takes a fresh array filled for this join
-    const bool reuse = !(zf && zf[0] == '0') && range + 1 <= kZlcMax;
+    const bool reuse = !env_is("DAS_ZLC", '0') && range + 1 <= kZlcMax;
     // from the first slot write until the build's own slots are cleared
     // again, any unwind (an allocation or launch failure, an expansion
     // throwing) leaves slots set: the guard drops the context's array, so the
@@ -2831,7 +2616,7 @@ std::unique_ptr<Table> direct_join(Ctx& c, const Table& P, const Table& Q, int32
       DAS_HIP(hipGetLastError());
     }
     if (!reuse) return expand(*Qb, lcp);
-    if (const char* t = std::getenv("DAS_TEST_ZLC_THROW"); t && t[0] == '1')   // tests: an unwind mid-join
+    if (env_is("DAS_TEST_ZLC_THROW", '1'))   // tests: an unwind mid-join
       DAS_CHECK(false, DAS_E_INTERNAL, "DAS_TEST_ZLC_THROW");
     std::unique_ptr<Table> out = expand(*Qb, lcp);
     hipLaunchKernelGGL(k_lc_clear, G(Q.nrows), dim3(B), 0, c.s, qkey, Q.nrows, kmin, (uint32_t)range, lcp);
@@ -3262,7 +3047,7 @@ int colof_t(const Table& t, int32_t v) {
 }
 
 IjKeys ij_keys(const PosIndex& PI, uint32_t type_id) {
-  static const bool no_dir = std::getenv("DAS_NO_KEY_DIR") != nullptr;
+  static const bool no_dir = env_set("DAS_NO_KEY_DIR");
   const bool use_rank = type_id < PI.rbits.size() && PI.rbits[type_id] && !no_dir;
   const bool use_dir = !use_rank && type_id < PI.dir.size() && PI.dir[type_id] && !no_dir;
   const bool use_bdir = !use_rank && !use_dir && type_id < PI.bdir.size() && PI.bdir[type_id] && !no_dir;
@@ -3376,15 +3161,15 @@ bool ij_prepare(Ctx& c, const Table& A, const das_link_scan_t& q, uint64_t rows,
     }
   }
   // cost: a search per row of A against a scan of the Link's type segment
+  const char ij = env_char("DAS_INDEX_JOIN");          // tests: 1 always, 0 never
   {
-    const char* f = std::getenv("DAS_INDEX_JOIN");          // tests: 1 always, 0 never
-    if (f && f[0] == '0') return false;
+    if (ij == '0') return false;
     const uint64_t seg = idx.type_off[ar].size() > q.type_id + 1
                              ? idx.type_off[ar][q.type_id + 1] - idx.type_off[ar][q.type_id] : 0;
     // (with grounded targets the scan reads one key range, of unknown size
     // here: index-join only small probes)
     const bool cheap = g.n == 0 ? 4 * rows <= seg : rows <= (1ull << 20);
-    if (!(f && f[0] == '1') && !cheap) return false;
+    if (ij != '1' && !cheap) return false;
   }
   DAS_CHECK(PI.t.rows < 0xFFFFFFFFull, DAS_E_UNSUPPORTED, "index join: P table too large");
   // output schema: A's variables and the fresh ones, ascending
@@ -3426,11 +3211,11 @@ bool ij_prepare(Ctx& c, const Table& A, const das_link_scan_t& q, uint64_t rows,
     // ranged mode: the rows of a grounded key (type, t_q = v) of P_{a,q},
     // when they are few (found in the host key mirror) and ordered by the
     // probe's position once the grounded targets before it are fixed
-    const char* f = std::getenv("DAS_IJ_RANGED");          // tests: 1 whenever possible, 0 never
+    const char rg = env_char("DAS_IJ_RANGED");          // tests: 1 whenever possible, 0 never
     uint64_t best = ~0ull;
     IjGround gb{};
     uint32_t blo = 0, bhi = 0, bq = 0;
-    for (uint32_t qq = 0; qq < ar && !(f && f[0] == '0'); ++qq) {
+    for (uint32_t qq = 0; qq < ar && rg != '0'; ++qq) {
       if (q.target[qq] == kNone) continue;
       const PosIndex& PQ = idx.pidx[ar][qq];
       if (PQ.h_ukey.empty() || PQ.t.rows >= 0xFFFFFFFFull) continue;
@@ -3472,12 +3257,11 @@ bool ij_prepare(Ctx& c, const Table& A, const das_link_scan_t& q, uint64_t rows,
     // index join then (DAS_INDEX_JOIN=1 / DAS_IJ_RANGED=1 keep it)
     // (dir_only: the fused chain's probes after a partitioned scan -- the
     // key-directory lookup instead of that search, no scan)
-    const char* fij = std::getenv("DAS_INDEX_JOIN");
-    const bool long_range = best != ~0ull && best > 0 && rows > 4096 && !(f && f[0] == '1') &&
+    const bool long_range = best != ~0ull && best > 0 && rows > 4096 && rg != '1' &&
                             (double)rows * std::log2((double)best) > 2.0 * (double)best;
-    if (long_range && !dir_only && !(fij && fij[0] == '1')) return false;
+    if (long_range && !dir_only && ij != '1') return false;
     const bool take = best != ~0ull && !(dir_only && long_range) &&
-                      ((f && f[0] == '1') || (best <= (1ull << 22) && best <= 64ull * rows));
+                      (rg == '1' || (best <= (1ull << 22) && best <= 64ull * rows));
     if (take) {
       g = gb;
       kx.fixed = 1;
@@ -3542,8 +3326,8 @@ std::unique_ptr<Table> index_join(Ctx& c, const Table& A, const das_link_scan_t&
       }
     }
     if (!out && A.nrows > kIjSmall && A.nrows <= kIjMid) {
-      const char* f = std::getenv("DAS_IJ_MID");                // A/B, tests: 0 never
-      if (!(f && f[0] == '0')) {
+      // A/B, tests: 0 never
+      if (!env_is("DAS_IJ_MID", '0')) {
         // one launch when the output fits a speculative table of 4 rows per probe row
         auto t = new_table(c, DAS_TABLE_ORDERED, nu, pl.uni.data(), std::max<uint64_t>(65536, 4 * A.nrows));
         DBuf<uint32_t> ctr(3, c.s);
@@ -4086,8 +3870,7 @@ bool chain_grid_wanted(Ctx& c, const std::vector<const das_plan_node_t*>& terms,
     // on the GPU against 47 us for the scan + direct join, and the batched
     // step 0.250-0.268 vs 0.212-0.226 ms (profiles/r5_flybase_env_ab.txt)
     if (k == 0 && r > kGridSeg) {
-      const char* ps = std::getenv("DAS_CHAIN_PSCAN");
-      return ps && ps[0] == '1' && terms[1]->op == DAS_PLAN_LINK && terms[1]->index_join && r <= part_scan_max(c);
+      return env_is("DAS_CHAIN_PSCAN", '1') && terms[1]->op == DAS_PLAN_LINK && terms[1]->index_join && r <= part_scan_max(c);
     }
     if (r > kGridSeg) return false;
     bound *= std::max<uint64_t>(r, 1);
@@ -4124,10 +3907,10 @@ int chain_finish(Ctx& c, ChainRun& R, bool& matched, std::unique_ptr<Table>& out
 // whether fused_and applies, and the form it would take first (grid or not)
 int fused_and_form(Ctx& c, const std::vector<const das_plan_node_t*>& terms,
                    const std::vector<const das_plan_node_t*>& anti, int no_overload) {
-  const char* f = std::getenv("DAS_FUSED");                  // tests: 0 never
-  if ((f && f[0] == '0') || no_overload || terms.empty()) return -1;
-  const char* gm = std::getenv("DAS_CHAIN_GRID");
-  const bool want_grid = !(gm && gm[0] == '0') && chain_grid_wanted(c, terms, anti.size(), gm && gm[0] == '1');
+  // tests: 0 never
+  if (env_is("DAS_FUSED", '0') || no_overload || terms.empty()) return -1;
+  const char gm = env_char("DAS_CHAIN_GRID");
+  const bool want_grid = gm != '0' && chain_grid_wanted(c, terms, anti.size(), gm == '1');
   if (trace_on()) trace_mark(want_grid ? "chain grid" : "chain one workgroup");
   return want_grid ? 1 : 0;
 }
@@ -4143,10 +3926,7 @@ int fused_and(Ctx& c, const std::vector<const das_plan_node_t*>& terms,
   // no k_chain_prep launch -- FlyBase F5 / F6 / F7 46.7 / 39.4 / 56.8 vs
   // 50.2 / 43.7 / 61.4 us per query, the matched() step 0.236-0.251 vs
   // 0.257-0.280 ms (round 6, one box, 9 of 10 alternating pairs).
-  // DAS_CHAIN_PREP1=1: the prep launch (fresh counters, the descriptor
-  // copied to device memory once).
-  const char* cp = std::getenv("DAS_CHAIN_PREP1");
-  uint32_t* gsc = cp && cp[0] == '1' ? nullptr : c.gsc_block(kPubPool + (uint32_t)pub_level());
+  uint32_t* gsc = c.gsc_block((uint32_t)pub_level());
   for (int attempt = form == 1 ? 0 : 1; attempt < 2; ++attempt) {
     ChainRun R;
     const int r = chain_compile(c, terms, anti, attempt == 0, R, gsc);
@@ -4567,15 +4347,11 @@ ChainRunPtr fused_and_launch(Ctx& c, const std::vector<const das_plan_node_t*>& 
     }
     c.s = ss;
   }
-  // DAS_CHAIN_PREP=0: pooled zeroed counters and every workgroup reading the
-  // descriptor from pinned memory, no k_chain_prep launch -- measured no
-  // faster (FlyBase step 0.235 / 0.254 vs 0.230 / 0.234 ms with the prep,
-  // profiles/r5_flybase_env_ab.txt), so the prep stays the default
-  const char* fp = std::getenv("DAS_CHAIN_PREP");
-  uint32_t* gsc = fp && fp[0] == '0' ? c.gsc_block(k) : nullptr;
+  // (a batch's grid chains take fresh counters zeroed by k_chain_prep: the
+  // pooled block of the one-at-a-time form measured no faster here)
   for (int attempt = form == 1 ? 0 : 1; attempt < 2; ++attempt) {
     ChainRunPtr R(new ChainRun);
-    const int r = chain_compile(c, terms, anti, attempt == 0, *R, gsc);
+    const int r = chain_compile(c, terms, anti, attempt == 0, *R);
     if (r < 0) continue;
     if (r == 0 || !R->complete) return nullptr;
     chain_launch(c, *R, pub_reserve_pool(k), pinned_stage_pool(k, chain_stage_bytes(*R)), side, k);
@@ -4595,8 +4371,8 @@ int fused_and_finish(Ctx& c, ChainRun& R, bool& matched, std::unique_ptr<Table>&
 
 int fused_or(Ctx& c, const std::vector<const das_plan_node_t*>& terms, int no_overload, bool& matched,
              std::unique_ptr<Table>& out, UnionRun* defer) {
-  const char* f = std::getenv("DAS_FUSED");                  // tests: 0 never
-  if ((f && f[0] == '0') || no_overload || terms.size() < 2 || terms.size() + 1 > (size_t)kChainStages) return 0;
+  // tests: 0 never
+  if (env_is("DAS_FUSED", '0') || no_overload || terms.size() < 2 || terms.size() + 1 > (size_t)kChainStages) return 0;
   Index& idx = c.idx;
   std::vector<ScanPrep> preps(terms.size());
   uint64_t total = 0;
@@ -4614,8 +4390,8 @@ int fused_or(Ctx& c, const std::vector<const das_plan_node_t*>& terms, int no_ov
   if (total == 0) return 0;
   bool single = true;
   for (auto& P : preps) single = single && (P.empty || P.ranges.size() == 1);
-  const char* fm = std::getenv("DAS_UNION_MULTI");            // tests: 1 = always the multi-launch form
-  const bool multi = total > kChainHash / 2 || !single || (fm && fm[0] == '1');
+  // tests: 1 = always the multi-launch form
+  const bool multi = total > kChainHash / 2 || !single || env_is("DAS_UNION_MULTI", '1');
   if (defer && !multi) return 0;                              // deferred: the union launch only
   if (multi) {
     // larger: every range of every term counted in one launch, written in
@@ -4660,7 +4436,6 @@ int fused_or(Ctx& c, const std::vector<const das_plan_node_t*>& terms, int no_ov
                   scanned < 0xFFFFFFF0ull;
       for (uint32_t i = 0; i < ms.nseg && proj; ++i)
         proj = !ms.seg[i].sp.unordered && !ms.seg[i].sp.emit_link && ms.seg[i].sp.nout == 1;
-      const char* fb = std::getenv("DAS_UNION_BITS");                // A/B, tests: 0 never
       // (its segments re-chunked by B rows: one row per thread)
       MultiScan ms1 = ms;
       uint64_t blocks = 0;
@@ -4669,8 +4444,9 @@ int fused_or(Ctx& c, const std::vector<const das_plan_node_t*>& terms, int no_ov
         blocks += (ms1.seg[i].end - ms1.seg[i].begin + B - 1) / B;
       }
       proj = proj && blocks < (1ull << 32) / B;                 // the dispatch grid counts work-items in 32 bits
-      if (defer && !(proj && !(fb && fb[0] == '0'))) return 0;   // deferred: the union launch only
-      if (proj && !(fb && fb[0] == '0')) {
+      const bool bits = proj && !env_is("DAS_UNION_BITS", '0');      // A/B, tests: 0 never
+      if (defer && !bits) return 0;                               // deferred: the union launch only
+      if (bits) {
         const uint32_t range = uhi[0] - ulo[0] + 1;
         auto res = new_table(c, DAS_TABLE_ORDERED, 1, preps[0].vars, scanned);
         // (a fresh, filled bitmap per union: a context-level all-zero bitmap
@@ -4863,8 +4639,8 @@ struct BitsPred {
 };
 
 std::unique_ptr<Table> semi_join(Ctx& c, const Table& P, const Table& Q) {
-  const char* f = std::getenv("DAS_SEMI_JOIN");           // tests: 0 never
-  if (f && f[0] == '0') return nullptr;
+  // tests: 0 never
+  if (env_is("DAS_SEMI_JOIN", '0')) return nullptr;
   const int32_t var = Q.vars[0];
   int pk = -1;
   for (int i = 0; i < P.ncols; ++i) if (P.vars[i] == var) pk = i;
@@ -5022,43 +4798,27 @@ std::unique_ptr<Table> index_join_filtered(Ctx& c, const Table& A, const das_lin
   const uint64_t total = scan_total<uint64_t>(SpanIn<uint64_t>{tot.p}, units, toff.p, c.s);
   if (!total) return new_table(c, DAS_TABLE_ORDERED, nu, pl.uni.data(), 0);
   if (total >= (1ull << 32) - (1ull << 16)) return nullptr;
-  const uint64_t chunks = (total + kBalChunk - 1) / kBalChunk;
-  const unsigned fgrid = grid_for(chunks, B / 64, 65535u * 4u);
   const FiltKey fk{jc.b[fb], (uint32_t)lo, (uint32_t)(hi - lo + 1), (const uint32_t*)bits.p, fb};
-  // DAS_FILT_FUSED=1: one pass, unsorted output, while the worst case (every
-  // virtual output kept) fits the output buffer.  Off by default: at config 5
-  // it ran 924 us against 337 + 296 us for the two ordered passes (round 3,
-  // profiles/archive/r3_hub_filt_ab.json) -- the LDS flag tiles cut its occupancy
-  const char* ff = std::getenv("DAS_FILT_FUSED");
-  if (ff && ff[0] == '1' && (uint64_t)nu * total * 4 <= (16ull << 30)) {
-    const unsigned ugrid = grid_for((chunks + (B / 64) * kFuseChunks - 1) / ((B / 64) * kFuseChunks), 1, 65535u * 4u);
-    auto out = new_table(c, DAS_TABLE_ORDERED, nu, pl.uni.data(), total);
-    DBuf<unsigned long long> kept(1, c.s);
-    fill_dev(kept.p, 0, 8, c.s);
-    const bool spec = (jc.np == 1 && jc.nb == 1) || (jc.np == 2 && jc.nb == 1) || (jc.np == 1 && jc.nb == 2);
-    {
-      // per probe row its row id, (first, count) and probe columns; per
-      // output its build value and (kept) its build columns; kept outputs out
-      ProfScope ps(c, spec ? "k_dj_filt_fused<" + std::to_string(jc.np) + "," + std::to_string(jc.nb) + ">"
-                           : std::string("k_dj_filt_fused<-1,-1>"),
-                   (12.0 + 4.0 * jc.np) * A.nrows + 4.0 * total);
-#define FILT_F(NPV, NBV)                                                                                          \
-  hipLaunchKernelGGL((k_dj_filt_fused<NPV, NBV>), dim3(ugrid), dim3(B), 0, c.s, (const uint32_t*)rowid.p, A.nrows, 0u, \
-                     (uint32_t)A.nrows, (const uint2*)lc.p, units, (const uint64_t*)toff.p, total, fk, jc, out->data,  \
-                     out->cap, kept.p)
-      if (jc.np == 1 && jc.nb == 1) FILT_F(1, 1);
-      else if (jc.np == 2 && jc.nb == 1) FILT_F(2, 1);
-      else if (jc.np == 1 && jc.nb == 2) FILT_F(1, 2);
-      else FILT_F(-1, -1);
-#undef FILT_F
-      DAS_HIP(hipGetLastError());
-    }
-    out->nrows = read_u64(reinterpret_cast<const uint64_t*>(kept.p), c.s);
-    // the kept outputs' columns written (bytes known only now: charged to the scope's launch below)
-    prof_add_bytes(c, spec ? "k_dj_filt_fused<" + std::to_string(jc.np) + "," + std::to_string(jc.nb) + ">"
-                           : std::string("k_dj_filt_fused<-1,-1>"),
-                   (4.0 * nu) * out->nrows);
-    out->sorted_col = -1;                          // chunks land in completion order
+  // The kernels are specialised on the output column counts (np, nb) of three
+  // shapes and read them from jc otherwise (-1, -1): with_shape calls
+  // launch(NP, NB) with the counts as compile-time constants, and targs is
+  // the tail of rocprof's name of that instantiation.
+  const bool spec = (jc.np == 1 && jc.nb == 1) || (jc.np == 2 && jc.nb == 1) || (jc.np == 1 && jc.nb == 2);
+  const std::string targs = spec ? std::to_string(jc.np) + "," + std::to_string(jc.nb) + ">" : std::string("-1,-1>");
+  auto with_shape = [&](auto&& launch) {
+    using std::integral_constant;
+    if (!spec) launch(integral_constant<int, -1>{}, integral_constant<int, -1>{});
+    else if (jc.np == 2) launch(integral_constant<int, 2>{}, integral_constant<int, 1>{});
+    else if (jc.nb == 2) launch(integral_constant<int, 1>{}, integral_constant<int, 2>{});
+    else launch(integral_constant<int, 1>{}, integral_constant<int, 1>{});
+    DAS_HIP(hipGetLastError());
+  };
+  const uint32_t* const rows = rowid.p;
+  const uint2* const lcp = lc.p;
+  const uint64_t* const offp = toff.p;
+  const uint32_t nrows = (uint32_t)A.nrows;
+  auto finish = [&](std::unique_ptr<Table> out) {
+    out->sorted_col = A.sorted_col >= 0 ? colof_t(*out, A.vars[A.sorted_col]) : -1;
     for (int k = 0; k < nu; ++k) {
       out->lo[k] = pl.lo[k];
       out->hi[k] = pl.hi[k];
@@ -5066,29 +4826,21 @@ std::unique_ptr<Table> index_join_filtered(Ctx& c, const Table& A, const das_lin
     out->lo[fo] = (uint32_t)lo;
     out->hi[fo] = (uint32_t)hi;
     return out;
-  }
-  // outputs per wave chunk of the two passes (DAS_FILT_CHUNK: 1024 / 2048 / 4096, A/B)
-  static const int ch = [] {
-    const char* e = std::getenv("DAS_FILT_CHUNK");
-    const int v = e ? std::atoi(e) : 0;
-    return v == 2048 || v == 4096 ? v : 1024;
-  }();
-  const uint64_t fchunks = (total + ch - 1) / ch;
-  const unsigned fgrid2 = grid_for(fchunks, B / 64, 65535u * 4u);
+  };
   // one walk writing kept outputs chunk-locally (k_dj_filt<2>) + a
   // compaction of the chunk runs: config 5's H4 0.82 -> 0.71 ms against the
   // flag pass and a second walk (DAS_FILT_LOCAL=0, A/B;
   // profiles/archive/r3_hub_local_ab.json)
-  const char* fle = std::getenv("DAS_FILT_LOCAL");
-  const bool local = !(fle && fle[0] == '0');
+  const bool local = !env_is("DAS_FILT_LOCAL", '0');
   // its scratch holds every virtual output's columns (4 nu B each, against one
-  // flag byte per output for the two passes): taken while that stays within
-  // 16 GiB and half the device's free memory, and falls back to the two
-  // passes when the allocation fails (DAS_FILT_SCRATCH_MAX caps it, tests)
-  const uint64_t scr_bytes = (uint64_t)nu * total * 4;
-  const char* sme = std::getenv("DAS_FILT_SCRATCH_MAX");
-  const uint64_t scr_cap = sme ? std::strtoull(sme, nullptr, 10) : (16ull << 30);
-  bool fits = local && ch == 1024 && scr_bytes <= scr_cap;
+  // flag byte per output for the two passes; the column stride padded to 64
+  // rows, so every column starts 16-byte aligned for the staged walk's
+  // stores): taken while that stays within 16 GiB and half the device's free
+  // memory, and falls back to the two passes when the allocation fails
+  // (DAS_FILT_SCRATCH_MAX caps it, tests)
+  const uint64_t scap = (total + 63) & ~63ull;
+  const uint64_t scr_bytes = (uint64_t)nu * scap * 4;
+  bool fits = local && scr_bytes <= (uint64_t)env_int("DAS_FILT_SCRATCH_MAX", 16ll << 30);
   if (fits && scr_bytes > (1ull << 30)) {
     size_t fr = 0, tot = 0;
     fits = hipMemGetInfo(&fr, &tot) == hipSuccess && scr_bytes <= fr / 2;
@@ -5096,7 +4848,7 @@ std::unique_ptr<Table> index_join_filtered(Ctx& c, const Table& A, const das_lin
   DBuf<uint32_t> scr;
   if (fits) {
     try {
-      scr.alloc((uint64_t)nu * total, c.s);
+      scr.alloc((uint64_t)nu * scap, c.s);
     } catch (const Error&) {
       (void)hipGetLastError();
       fits = false;                                   // out of memory: the two passes below
@@ -5107,79 +4859,39 @@ std::unique_ptr<Table> index_join_filtered(Ctx& c, const Table& A, const das_lin
     // writes them to the chunk's slots of the scratch with 16-byte stores
     // (k_dj_filt_staged, 512-output chunks): the walk itself 429 -> 228 us at
     // config 5 (each lane's scattered 4-byte stores were the cost).
-    // DAS_FILT_STAGED=0: the unstaged walk (k_dj_filt<2>, 1024-output chunks);
-    // =atomic: the staged rows placed straight in the output by one atomic
-    // per chunk, no scratch, no compaction -- 1,600 us: 1.2 * 10^5 atomics on
-    // one address from 8 XCDs serialise (A/B record, output unsorted)
-    const char* se = std::getenv("DAS_FILT_STAGED");
-    const bool spec = (jc.np == 1 && jc.nb == 1) || (jc.np == 2 && jc.nb == 1) || (jc.np == 1 && jc.nb == 2);
-    const bool staged = !(se && se[0] == '0') && spec && nu == jc.np + jc.nb;
-    const bool atomic_place = staged && se && !std::strcmp(se, "atomic");
-    const uint64_t sch = staged ? 512 : 1024;
+    // DAS_FILT_STAGED=0: the unstaged walk (k_dj_filt<2>, 1024-output chunks)
+    const bool staged = !env_is("DAS_FILT_STAGED", '0') && spec && nu == jc.np + jc.nb;
+    const uint64_t sch = staged ? (uint64_t)kStageChunk : kBalChunk;
     const uint64_t nch = (total + sch - 1) / sch;
     const unsigned sgrid = grid_for(nch, B / 64, 65535u * 4u);
     DBuf<uint32_t> ccnt(nch, c.s), coff(nch + 1, c.s);
-    DBuf<unsigned long long> kept;
-    std::unique_ptr<Table> direct_out;
-    if (atomic_place) {
-      direct_out = new_table(c, DAS_TABLE_ORDERED, nu, pl.uni.data(), total);
-      kept.alloc(1, c.s);
-      fill_dev(kept.p, 0, 8, c.s);
-    }
-    // the chunks' first units (DAS_FILT_CUNIT=0: the walk searches them)
-    const char* cue = std::getenv("DAS_FILT_CUNIT");
-    const bool cun = staged && !(cue && cue[0] == '0') && units < (1ull << 32);
+    // the chunks' first units (2^32 units or more: the walk searches them)
     DBuf<uint32_t> cunit;
-    if (cun) {
+    if (staged && units < (1ull << 32)) {
       cunit.alloc(nch, c.s);
       KScope ks("k_chunk_units", 4.0 * nch);
-      hipLaunchKernelGGL(k_chunk_units<512>, G(nch), dim3(B), 0, c.s, (const uint64_t*)toff.p, units, nch, cunit.p);
+      hipLaunchKernelGGL(k_chunk_units, G(nch), dim3(B), 0, c.s, offp, units, nch, cunit.p);
       DAS_HIP(hipGetLastError());
     }
-    const std::string nm = staged ? "k_dj_filt_staged<" + std::to_string(jc.np) + "," + std::to_string(jc.nb) + ",512>"
-                           : spec ? "k_dj_filt<2," + std::to_string(jc.np) + "," + std::to_string(jc.nb) + ",1024,4>"
-                                  : std::string("k_dj_filt<2,-1,-1,1024,4>");
+    const uint32_t* const cup = cunit.p;
+    const std::string nm = (staged ? "k_dj_filt_staged<" : "k_dj_filt<2,") + targs;
     {
       // per probe row its row id, (first, count) and probe columns; per
       // output its build value (a P row); kept outputs' columns written
       ProfScope ps(c, nm, (12.0 + 4.0 * jc.np) * A.nrows + 4.0 * total);
-#define FILT_S(NPV, NBV)                                                                                         \
-  hipLaunchKernelGGL((k_dj_filt_staged<NPV, NBV, 512>), dim3(sgrid), dim3(B), 0, c.s, (const uint32_t*)nullptr,    \
-                     A.nrows, 0u, (uint32_t)A.nrows, (const uint2*)lc.p, units, (const uint64_t*)toff.p, total, fk, \
-                     jc, atomic_place ? direct_out->data : scr.p, atomic_place ? direct_out->cap : total, 0ull, nch, \
-                     atomic_place ? (uint32_t*)nullptr : ccnt.p, atomic_place ? kept.p : nullptr, \
-                     cun ? (const uint32_t*)cunit.p : nullptr)
-#define FILT_L(NPV, NBV)                                                                                       \
-  hipLaunchKernelGGL((k_dj_filt<2, NPV, NBV, 1024>), dim3(sgrid), dim3(B), 0, c.s, (const uint32_t*)rowid.p, A.nrows, \
-                     0u, (uint32_t)A.nrows, (const uint2*)lc.p, units, (const uint64_t*)toff.p, total, fk,             \
-                     (uint8_t*)nullptr, ccnt.p, (const uint32_t*)nullptr, jc, scr.p, total, 0ull, nch)
-      if (staged) {
-        if (jc.np == 1 && jc.nb == 1) FILT_S(1, 1);
-        else if (jc.np == 2 && jc.nb == 1) FILT_S(2, 1);
-        else FILT_S(1, 2);
-      } else if (jc.np == 1 && jc.nb == 1) FILT_L(1, 1);
-      else if (jc.np == 2 && jc.nb == 1) FILT_L(2, 1);
-      else if (jc.np == 1 && jc.nb == 2) FILT_L(1, 2);
-      else FILT_L(-1, -1);
-#undef FILT_S
-#undef FILT_L
-      DAS_HIP(hipGetLastError());
-    }
-    auto finish = [&](std::unique_ptr<Table> out, int sorted) {
-      out->sorted_col = sorted;
-      for (int k = 0; k < nu; ++k) {
-        out->lo[k] = pl.lo[k];
-        out->hi[k] = pl.hi[k];
-      }
-      out->lo[fo] = (uint32_t)lo;
-      out->hi[fo] = (uint32_t)hi;
-      return out;
-    };
-    if (atomic_place) {
-      const uint64_t m = read_u64(reinterpret_cast<const uint64_t*>(kept.p), c.s);
-      prof_add_bytes(c, nm, 4.0 * nu * m);
-      direct_out->nrows = m;
-      return finish(std::move(direct_out), -1);               // chunks land in completion order
+      with_shape([&](auto NP, auto NB) {
+        if constexpr (NP() > 0) {
+          if (staged) {
+            hipLaunchKernelGGL((k_dj_filt_staged<NP(), NB()>), dim3(sgrid), dim3(B), 0, c.s, (const uint32_t*)nullptr,
+                               A.nrows, 0u, nrows, lcp, units, offp, total, fk, jc, scr.p, scap, 0ull, nch, ccnt.p,
+                               cup);
+            return;
+          }
+        }
+        hipLaunchKernelGGL((k_dj_filt<2, NP(), NB()>), dim3(sgrid), dim3(B), 0, c.s, rows, A.nrows, 0u, nrows, lcp,
+                           units, offp, total, fk, (uint8_t*)nullptr, ccnt.p, (const uint32_t*)nullptr, jc, scr.p, scap,
+                           0ull, nch);
+      });
     }
     const uint64_t m = scan_total<uint32_t>(SpanIn<uint32_t>{ccnt.p}, nch, coff.p, c.s);
     prof_add_bytes(c, nm, 4.0 * nu * m);
@@ -5188,89 +4900,42 @@ std::unique_ptr<Table> index_join_filtered(Ctx& c, const Table& A, const das_lin
     if (m) {
       KScope ks(staged ? "k_chunk_compact<512>" : "k_chunk_compact<1024>", 8.0 * nu * m + 8.0 * nch);
       if (staged)
-        hipLaunchKernelGGL(k_chunk_compact<512>, dim3(sgrid), dim3(B), 0, c.s, (const uint32_t*)scr.p, total,
+        hipLaunchKernelGGL(k_chunk_compact<kStageChunk>, dim3(sgrid), dim3(B), 0, c.s, (const uint32_t*)scr.p, scap,
                            (const uint32_t*)ccnt.p, (const uint32_t*)coff.p, 0ull, nch, nu, out->data, out->cap);
       else
-        hipLaunchKernelGGL(k_chunk_compact<1024>, dim3(sgrid), dim3(B), 0, c.s, (const uint32_t*)scr.p, total,
+        hipLaunchKernelGGL(k_chunk_compact<(int)kBalChunk>, dim3(sgrid), dim3(B), 0, c.s, (const uint32_t*)scr.p, scap,
                            (const uint32_t*)ccnt.p, (const uint32_t*)coff.p, 0ull, nch, nu, out->data, out->cap);
       DAS_HIP(hipGetLastError());
     }
-    const int sorted = A.sorted_col >= 0 ? colof_t(*out, A.vars[A.sorted_col]) : -1;
-    return finish(std::move(out), sorted);
+    return finish(std::move(out));
   }
+  // the two passes, in chunks of kBalChunk outputs
+  const uint64_t chunks = (total + kBalChunk - 1) / kBalChunk;
+  const unsigned fgrid = grid_for(chunks, B / 64, 65535u * 4u);
   DBuf<uint8_t> fl(total, c.s);
-  DBuf<uint32_t> ccnt(fchunks, c.s), coff(fchunks + 1, c.s);
+  DBuf<uint32_t> ccnt(chunks, c.s), coff(chunks + 1, c.s);
   {
     // per probe row its row id and (first, count); per output its build
     // value (a P row) and its flag byte
-    // (xu: see DAS_FILT_UNROLL below; the scope names rocprof's instantiation)
-    static const int xu0 = [] {
-      const char* e = std::getenv("DAS_FILT_UNROLL");
-      const int v = e ? std::atoi(e) : 0;
-      return v == 8 || v == 16 ? v : 4;
-    }();
-    ProfScope ps(c, "k_dj_filt<0,-1,-1," + std::to_string(ch) + "," + std::to_string(ch == 1024 ? xu0 : 4) + ">",
-                 12.0 * A.nrows + 5.0 * total);
-#define FILT_0(CHV)                                                                                                \
-  hipLaunchKernelGGL((k_dj_filt<0, -1, -1, CHV>), dim3(fgrid2), dim3(B), 0, c.s, (const uint32_t*)rowid.p, A.nrows,   \
-                     0u, (uint32_t)A.nrows, (const uint2*)lc.p, units, (const uint64_t*)toff.p, total, fk, fl.p, ccnt.p, \
-                     (const uint32_t*)nullptr, jc, (uint32_t*)nullptr, 0ull, 0ull, fchunks)
-    // DAS_FILT_UNROLL (8 / 16): rounds of 64 outputs whose build values and
-    // bitmap words are loaded together in the flag pass (A/B; default 4)
-    static const int xu = [] {
-      const char* e = std::getenv("DAS_FILT_UNROLL");
-      const int v = e ? std::atoi(e) : 0;
-      return v == 8 || v == 16 ? v : 4;
-    }();
-    if (ch == 2048) FILT_0(2048);
-    else if (ch == 4096) FILT_0(4096);
-    else if (xu == 8)
-      hipLaunchKernelGGL((k_dj_filt<0, -1, -1, 1024, 8>), dim3(fgrid2), dim3(B), 0, c.s, (const uint32_t*)rowid.p,
-                         A.nrows, 0u, (uint32_t)A.nrows, (const uint2*)lc.p, units, (const uint64_t*)toff.p, total, fk,
-                         fl.p, ccnt.p, (const uint32_t*)nullptr, jc, (uint32_t*)nullptr, 0ull, 0ull, fchunks);
-    else if (xu == 16)
-      hipLaunchKernelGGL((k_dj_filt<0, -1, -1, 1024, 16>), dim3(fgrid2), dim3(B), 0, c.s, (const uint32_t*)rowid.p,
-                         A.nrows, 0u, (uint32_t)A.nrows, (const uint2*)lc.p, units, (const uint64_t*)toff.p, total, fk,
-                         fl.p, ccnt.p, (const uint32_t*)nullptr, jc, (uint32_t*)nullptr, 0ull, 0ull, fchunks);
-    else FILT_0(1024);
-#undef FILT_0
+    ProfScope ps(c, "k_dj_filt<0,-1,-1>", 12.0 * A.nrows + 5.0 * total);
+    hipLaunchKernelGGL((k_dj_filt<0, -1, -1>), dim3(fgrid), dim3(B), 0, c.s, rows, A.nrows, 0u, nrows, lcp, units, offp,
+                       total, fk, fl.p, ccnt.p, (const uint32_t*)nullptr, jc, (uint32_t*)nullptr, 0ull, 0ull, chunks);
     DAS_HIP(hipGetLastError());
   }
-  const uint64_t m = scan_total<uint32_t>(SpanIn<uint32_t>{ccnt.p}, fchunks, coff.p, c.s);
+  const uint64_t m = scan_total<uint32_t>(SpanIn<uint32_t>{ccnt.p}, chunks, coff.p, c.s);
   auto out = new_table(c, DAS_TABLE_ORDERED, nu, pl.uni.data(), m);
   out->nrows = m;
   if (m) {
     // + the probe columns, the flags, the kept outputs' build rows and their columns out
-    // (named as rocprof names the instantiation launched below)
-    const bool spec = (jc.np == 1 && jc.nb == 1) || (jc.np == 2 && jc.nb == 1) || (jc.np == 1 && jc.nb == 2);
-    const std::string chs4 = "," + std::to_string(ch) + ",4>";
-    ProfScope ps(c, spec ? "k_dj_filt<1," + std::to_string(jc.np) + "," + std::to_string(jc.nb) + chs4
-                         : "k_dj_filt<1,-1,-1" + chs4,
+    ProfScope ps(c, "k_dj_filt<1," + targs,
                  (12.0 + 4.0 * jc.np) * A.nrows + 1.0 * total + 4.0 * jc.nb * m + 4.0 * nu * m);
-#define FILT_W(NPV, NBV, CHV)                                                                                  \
-  hipLaunchKernelGGL((k_dj_filt<1, NPV, NBV, CHV>), dim3(fgrid2), dim3(B), 0, c.s, (const uint32_t*)rowid.p, A.nrows, \
-                     0u, (uint32_t)A.nrows, (const uint2*)lc.p, units, (const uint64_t*)toff.p, total, fk, fl.p,      \
-                     (uint32_t*)nullptr, (const uint32_t*)coff.p, jc, out->data, out->cap, 0ull, fchunks)
-#define FILT_WC(CHV)                                    \
-  if (jc.np == 1 && jc.nb == 1) FILT_W(1, 1, CHV);      \
-  else if (jc.np == 2 && jc.nb == 1) FILT_W(2, 1, CHV); \
-  else if (jc.np == 1 && jc.nb == 2) FILT_W(1, 2, CHV); \
-  else FILT_W(-1, -1, CHV);
-    if (ch == 2048) { FILT_WC(2048) }
-    else if (ch == 4096) { FILT_WC(4096) }
-    else { FILT_WC(1024) }
-#undef FILT_WC
-#undef FILT_W
-    DAS_HIP(hipGetLastError());
+    with_shape([&](auto NP, auto NB) {
+      hipLaunchKernelGGL((k_dj_filt<1, NP(), NB()>), dim3(fgrid), dim3(B), 0, c.s, rows, A.nrows, 0u, nrows, lcp, units,
+                         offp, total, fk, fl.p, (uint32_t*)nullptr, (const uint32_t*)coff.p, jc, out->data, out->cap,
+                         0ull, chunks);
+    });
   }
-  out->sorted_col = A.sorted_col >= 0 ? colof_t(*out, A.vars[A.sorted_col]) : -1;
-  for (int k = 0; k < nu; ++k) {
-    out->lo[k] = pl.lo[k];
-    out->hi[k] = pl.hi[k];
-  }
-  out->lo[fo] = (uint32_t)lo;
-  out->hi[fo] = (uint32_t)hi;
-  return out;
+  return finish(std::move(out));
 }
 
 std::unique_ptr<Table> join(Ctx& c, const Table& A, const Table& Bt, int no_overload) {
@@ -5396,8 +5061,7 @@ std::unique_ptr<Table> join(Ctx& c, const Table& A, const Table& Bt, int no_over
 // Hash sets below 2^26 rows (a table of <= 2^28 slots); DAS_SET_SORT=1 forces
 // the sort-based path (tests cover both).
 bool use_hash_set(uint64_t n) {
-  const char* f = std::getenv("DAS_SET_SORT");
-  return n <= (1ull << 26) && !(f && f[0] == '1');
+  return n <= (1ull << 26) && !env_is("DAS_SET_SORT", '1');
 }
 uint32_t hset_mask(uint64_t n) {
   uint64_t m = 1024;

@@ -3,6 +3,7 @@
 // also builds with plain g++ for the sanitizer targets (Makefile: asan, tsan).
 #pragma once
 #include <cstdint>
+#include <cstdlib>
 #include <stdexcept>
 #include <string>
 
@@ -30,5 +31,22 @@ enum Status : int {
   do {                                             \
     if (!(cond)) throw ::das::Error((code), (msg)); \
   } while (0)
+
+// The DAS_* environment switches are read through these helpers and nowhere
+// else (here, not in das_internal.h: prims.h and the host-only reader use them
+// too).  A call site is `static` when the switch is read once per process and
+// plain when the tests flip it between calls; a site that tests one switch
+// against several values reads it once with env_char.
+inline const char* env_str(const char* name) { return std::getenv(name); }
+inline bool env_set(const char* name) { return env_str(name) != nullptr; }
+inline char env_char(const char* name) {          // the value's first character; 0: unset or empty
+  const char* e = env_str(name);
+  return e ? e[0] : '\0';
+}
+inline bool env_is(const char* name, char c) { return env_char(name) == c; }
+inline long long env_int(const char* name, long long dflt) {
+  const char* e = env_str(name);
+  return e ? std::strtoll(e, nullptr, 10) : dflt;
+}
 
 }  // namespace das

@@ -1,6 +1,7 @@
 """GPU parity: the HIP path (through the C ABI) against the reference's golden
 outputs and the CPU oracle, bit-exact (handles, binding sets)."""
 import hashlib
+import itertools
 import json
 import os
 
@@ -878,7 +879,7 @@ def test_gpu_hub_four_clause_matches_oracle(semi, monkeypatch):
         assert same(got, want), (name, got.get("n"), want.get("n"))
 
 
-@pytest.mark.parametrize("multi", ["1", "1-twopass", "1-local", "1-unstaged", "1-atomic", "1-capped", "0"])
+@pytest.mark.parametrize("multi", ["1", "1-twopass", "1-unstaged", "1-capped", "0"])
 def test_gpu_semi_join_multi_matches_oracle(multi, monkeypatch):
     """Runs of one-variable hub clauses on one variable (T2(V2,a), T3(V2,b),
     ...) folded by ONE filter with the intersection of their key sets
@@ -890,14 +891,12 @@ def test_gpu_semi_join_multi_matches_oracle(multi, monkeypatch):
     import bench
     from das_amd import synthetic
     monkeypatch.setenv("DAS_SEMI_MULTI", multi[0])
-    # the filtered expansion in one pass with LDS flag tiles (unsorted) ...
-    monkeypatch.setenv("DAS_FILT_FUSED", "0" if multi in ("1-twopass", "1-local", "1-unstaged", "1-atomic") else "1")
-    # ... as one walk writing chunk-locally + a compaction -- the kept rows
-    # staged in LDS (k_dj_filt_staged, default), or stored lane by lane
-    # (k_dj_filt<2>, DAS_FILT_STAGED=0), or placed by one atomic per chunk
-    # (=atomic, no compaction) -- or as a flag pass and a second walk
+    # the filtered expansion as one walk writing chunk-locally + a compaction
+    # -- the kept rows staged in LDS (k_dj_filt_staged, default), or stored
+    # lane by lane (k_dj_filt<2>, DAS_FILT_STAGED=0) -- or as a flag pass and a
+    # second walk
     monkeypatch.setenv("DAS_FILT_LOCAL", "0" if multi == "1-twopass" else "1")
-    monkeypatch.setenv("DAS_FILT_STAGED", {"1-unstaged": "0", "1-atomic": "atomic"}.get(multi, "1"))
+    monkeypatch.setenv("DAS_FILT_STAGED", "0" if multi == "1-unstaged" else "1")
     # ... and the one walk's scratch over its budget: the two passes instead
     if multi == "1-capped":
         monkeypatch.setenv("DAS_FILT_SCRATCH_MAX", "0")
@@ -932,6 +931,48 @@ def test_gpu_semi_join_multi_matches_oracle(multi, monkeypatch):
         assert same(got, want), (q, got.get("n"), want.get("n"))
         nonempty += want.get("n", 0) > 0
     assert nonempty >= 4
+
+
+def test_gpu_filtered_expansion_odd_total(monkeypatch):
+    """The one-walk filtered expansion with an odd virtual output count: its
+    scratch columns are then padded to a 64-row stride, so the staged walk's
+    16-byte stores stay aligned in every column.  A hub And
+    T(V1,h) T(V1,V2) T(V2,h'), its anchors and link types the first (in scan
+    order) for which the oracle gives an odd unfiltered join size above 512
+    -- more than one 512-output chunk -- and a non-empty answer.
+    8000 links, not the 4000 of the hub tests above: at 4000 the largest
+    T(V1,h) x T(V1,V2) over every anchor and type pair has 388 rows.
+    DAS_FUSED=0: a three-term And this small is otherwise one fused chain
+    launch and never reaches the expansion."""
+    import bench
+    from das_amd import synthetic
+    monkeypatch.setenv("DAS_SEMI_MULTI", "1")
+    monkeypatch.setenv("DAS_FUSED", "0")
+    arrays = synthetic.powerlaw_kb(200, 8000, link_types=4, seed=5)
+    odb = O.RedisMongoSemantics(O.KB.from_arrays(arrays))
+    n = lambda i: ["Node", "Concept", f"n{i}"]  # noqa: E731
+    V, L = bench._V, bench._L
+    T = [f"T{i}" for i in range(4)]
+    pick = None
+    for h, ta, tb in itertools.product(range(2), T, T):
+        join = [L(ta, V("V1"), n(h)), L(tb, V("V1"), V("V2"))]
+        total = O.evaluate(["And", join], odb).get("n", 0)
+        if total <= 512 or total % 2 == 0:
+            continue
+        for tc, h2 in itertools.product(T, range(3)):
+            q = ["And", join + [L(tc, V("V2"), n(h2))]]
+            want = O.evaluate(q, odb)
+            if want.get("n", 0) > 0:
+                pick = (q, total, want)
+                break
+        if pick:
+            break
+    assert pick is not None, "no anchors with an odd join size above 512 and a non-empty answer"
+    q, total, want = pick
+    assert total > 512 and total % 2 == 1, total
+    assert want.get("n", 0) > 0
+    got = record(q, _hipdb(arrays))
+    assert same(got, want), (q, total, got.get("n"), want.get("n"))
 
 
 @pytest.mark.parametrize("fused", ["1", "0"])
