@@ -80,6 +80,7 @@ NAME_STAGE_BYTES = 16384          # DAS_NAME_STAGE_BYTES: name bytes of one tile
 HALO_MAX_LEVELS = 8               # DAS_HALO_MAX_LEVELS
 HALO_BLOCK_ENTRIES = 1024         # DAS_HALO_BLOCK_ENTRIES: incoming-list entries one workgroup marks per pass
 PC_CHUNK_ROWS = 1024              # DAS_PC_CHUNK_ROWS: index rows one wave counts per step of a (1,2)-grounded template
+CJ_CHUNK_ROWS = 1024              # DAS_CJ_CHUNK_ROWS: driver rows one wave counts per step of a conjunction
 
 
 class das_plan_node_t(C.Structure):
@@ -126,6 +127,7 @@ _SIGS = {
     "das_node_name_stats": (C.c_int, [P, C.c_uint32, P, P, P]),
     "das_halo_expand": (C.c_int, [P, P, C.c_uint64, C.c_uint32, P, P]),
     "das_pattern_counts": (C.c_int, [P, P, P, C.c_uint64, C.POINTER(P)]),
+    "das_conjunction_counts": (C.c_int, [P, P, C.c_uint64, P, C.c_uint64, C.c_uint32, P]),
     "das_export_outgoing": (C.c_int, [P, P, P, P, P]),
     "das_counters": (C.c_int, [P]),
     "das_scan_link": (C.c_int, [P, C.POINTER(das_link_scan_t), C.POINTER(P)]),
@@ -605,6 +607,25 @@ class Context:
             check(lib().das_pattern_counts(self.h, None, ptr(ids) if ids.size else None, ids.size, C.byref(out)),
                   self.h)
         return Table(self, out).fetch()
+
+    def conjunction_counts(self, tpl, combos, k=None):
+        """Counts (uint64[n]) of n And-combinations of k templates
+        (das_conjunction_counts).  tpl: (5, m) uint32 -- arity, type id, t0,
+        t1, t2 (DAS_NONE = wildcard / unused); combos: (n, k) indices into
+        it (k is needed only for n = 0)."""
+        tpl = np.ascontiguousarray(np.asarray(tpl, dtype=np.uint32))
+        if tpl.ndim != 2 or tpl.shape[0] != 5:
+            raise ValueError("conjunction counts: templates are a 5 x m array")
+        combos = np.ascontiguousarray(np.asarray(combos, dtype=np.uint32))
+        if combos.ndim != 2 and k is None:
+            raise ValueError("conjunction counts: combinations are an n x k array")
+        k = combos.shape[1] if k is None else int(k)
+        n = combos.size // k if k else 0
+        out = np.zeros(n, dtype=np.uint64)
+        check(lib().das_conjunction_counts(self.h, ptr(tpl) if tpl.size else None, tpl.shape[1],
+                                           ptr(combos) if combos.size else None, n, k,
+                                           ptr(out) if n else None), self.h)
+        return out
 
     def ctype_lookup(self, digest):
         d = np.ascontiguousarray(np.asarray(digest, dtype=np.uint32))

@@ -560,6 +560,11 @@ int das_pattern_counts(das_ctx_t* ctx, const das_table_t* links, const uint32_t*
   });
 }
 
+int das_conjunction_counts(das_ctx_t* ctx, const uint32_t* tpl, uint64_t m, const uint32_t* combo, uint64_t n,
+                           uint32_t k, uint64_t* counts) {
+  return guarded(ctx, [&] { das::conjunction_counts(ctx->c, tpl, m, combo, n, k, counts); });
+}
+
 int das_ctype_lookup(das_ctx_t* ctx, const uint32_t digest[4], int64_t* ctype_id) {
   return guarded(ctx, [&] {
     const auto& v = ctx->c.idx.ctype_digest;

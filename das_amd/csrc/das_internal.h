@@ -390,6 +390,11 @@ void halo_expand(Ctx& c, const uint32_t* seed_ids, uint64_t n_seeds, uint32_t le
 // arity, type, t0, t1, t2 (kNone = wildcard or unused), count low / high word;
 // rows ordered by (arity, type, targets)
 std::unique_ptr<Table> pattern_counts(Ctx& c, const uint32_t* d_links, uint64_t n);
+// counts[c] = the rows of the natural join of the k templates combo[c * k ..]
+// (host, indices into the m host templates tpl: column-major arity, type, t0,
+// t1, t2; kNone = wildcard or unused) on V1 / V2 in wildcard order
+void conjunction_counts(Ctx& c, const uint32_t* tpl, uint64_t m, const uint32_t* combo, uint64_t n, uint32_t k,
+                        uint64_t* counts);
 
 // Column pointers of a table (kernel argument by value).
 struct ColSet {

@@ -1,6 +1,8 @@
-// SimplePatternMiner's two bulk steps on the device (das_halo_expand,
-// das_pattern_counts): the halo walk of notebook cell 6 and the template
-// support counts of build_patterns (cell 5).  DESIGN.md §3d.
+// SimplePatternMiner's bulk steps on the device (das_halo_expand,
+// das_pattern_counts, das_conjunction_counts): the halo walk of notebook cell
+// 6, the template support counts of build_patterns (cell 5) and the counts of
+// And-combinations of templates the mining loop asks for (at the end of this
+// file).  DESIGN.md §3d.
 //
 // Halo.  The state is four bitmaps over the atom ids (links seen / links of
 // this level / atoms expanded / atoms of this level).  A level is:
@@ -684,6 +686,326 @@ std::unique_ptr<Table> pattern_counts(Ctx& c, const uint32_t* d_links, uint64_t 
     DAS_HIP(hipGetLastError());
   }
   return out;
+}
+
+// ---------------------------------------------------------------------------
+// conjunction counts (das_conjunction_counts): the mining loop's compute_count
+// of And-combinations of templates, without a join output.  DESIGN.md §3d.
+//
+// A template binds V1, or (V1, V2), in wildcard order, and its rows in
+// P_{a,p} are sorted by (V1[, V2]): the natural join of k of them is an
+// intersection / semi-join, counted by walking one term's rows (the driver)
+// and probing the others by binary search.
+//   resolve  one thread per template -> CjTerm (row range, V1 / V2 columns,
+//            the filter of a (1,2)-grounded template)
+//   plan     one thread per combination: empty -> 0; else the driver and its
+//            chunk count (kCjChunk rows each)
+//   scan     exclusive scan of the chunk counts
+//   count    one wave per chunk, one add per wave
+// ---------------------------------------------------------------------------
+namespace {
+
+constexpr uint32_t kCjChunk = DAS_CJ_CHUNK_ROWS;          // driver rows of one wave step
+constexpr uint32_t kCjCoop = 64;                          // a longer sub-range is walked by the whole wave
+constexpr uint32_t kCjAllOne = 0, kCjDriveTwo = 1, kCjDriveOne = 2;   // plan modes (below)
+static_assert(kCjChunk % 64 == 0, "chunks are whole waves");
+
+struct CjTerm {
+  uint64_t lo, hi;           // its rows in one P_{a,p}; empty: no such key, or a black-listed type
+  const uint32_t* v1;        // the column bound to V1: ascending over [lo, hi)
+  const uint32_t* v2;        // the column bound to V2: ascending inside one V1 (null: one variable)
+  const uint32_t* fcol;      // targets (1,2) grounded: only the rows with fcol[r] == fval are the term's
+  uint32_t fval;             //   (the rows are sorted by (v1, fcol))
+  uint32_t nvars;
+};
+
+__global__ void k_cj_resolve(uint64_t m, const uint32_t* __restrict__ c_ar, const uint32_t* __restrict__ c_ty,
+                             const uint32_t* __restrict__ c_t0, const uint32_t* __restrict__ c_t1,
+                             const uint32_t* __restrict__ c_t2, PcIndex X, const uint8_t* __restrict__ blocked,
+                             CjTerm* terms) {
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < m; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t ar = c_ar[i], ty = c_ty[i];
+    const uint32_t T[3] = {c_t0[i], c_t1[i], ar == 3 ? c_t2[i] : kNone};
+    uint32_t ng = 0;
+    for (uint32_t p = 0; p < ar; ++p) ng += T[p] != kNone ? 1u : 0u;
+    CjTerm t{};
+    t.nvars = ar - ng;
+    uint64_t lo = 0, hi = 0;
+    if (!(blocked && blocked[ty])) {
+      if (ar == 2) {                           // [T, a, *] / [T, *, b]: the key range, V1 = the other target
+        const uint32_t p = T[0] != kNone ? 0u : 1u;
+        key_run(X.p2[p], ty, T[p], lo, hi);
+        t.v1 = X.p2[p].col[1 - p];
+      } else if (ng == 1) {                    // the key range, (V1, V2) = the other targets in position order
+        const uint32_t p = T[0] != kNone ? 0u : T[1] != kNone ? 1u : 2u;
+        key_run(X.p3[p], ty, T[p], lo, hi);
+        t.v1 = X.p3[p].col[p == 0 ? 1 : 0];
+        t.v2 = X.p3[p].col[p == 2 ? 1 : 2];
+      } else if (T[2] == kNone) {              // (0,1): rows of key t0 are sorted by (t1, t2)
+        if (key_run(X.p3[0], ty, T[0], lo, hi)) {
+          const uint64_t a = lower_row(X.p3[0].col[1], lo, hi, T[1]);
+          hi = lower_row(X.p3[0].col[1], a, hi, (uint64_t)T[1] + 1);
+          lo = a;
+        }
+        t.v1 = X.p3[0].col[2];
+      } else if (T[1] == kNone) {              // (0,2): rows of key t2 are sorted by (t0, t1)
+        if (key_run(X.p3[2], ty, T[2], lo, hi)) {
+          const uint64_t a = lower_row(X.p3[2].col[0], lo, hi, T[0]);
+          hi = lower_row(X.p3[2].col[0], a, hi, (uint64_t)T[0] + 1);
+          lo = a;
+        }
+        t.v1 = X.p3[2].col[1];
+      } else {                                 // (1,2): the shorter key range, filtered on the other target
+        uint64_t lo1, hi1, lo2, hi2;
+        const bool both = key_run(X.p3[1], ty, T[1], lo1, hi1) && key_run(X.p3[2], ty, T[2], lo2, hi2);
+        if (both && hi1 - lo1 <= hi2 - lo2) {
+          lo = lo1; hi = hi1;
+          t.v1 = X.p3[1].col[0]; t.fcol = X.p3[1].col[2]; t.fval = T[2];
+        } else if (both) {
+          lo = lo2; hi = hi2;
+          t.v1 = X.p3[2].col[0]; t.fcol = X.p3[2].col[1]; t.fval = T[1];
+        }
+      }
+    }
+    t.lo = lo;
+    t.hi = hi;
+    terms[i] = t;
+  }
+}
+
+// plan[c] = mode | driver << 2 | smallest two-variable term << 4 | (more than
+// one two-variable term) << 6, the two terms as positions in the combination.
+//   kCjAllOne    no two-variable term: drive the smallest term
+//   kCjDriveTwo  drive the smallest two-variable term, probe every other term
+//   kCjDriveOne  drive the smallest one-variable term (it has fewer rows than
+//                any two-variable one), probe the other one-variable terms,
+//                then take x's equal range in the smallest two-variable term
+__global__ void k_cj_plan(uint64_t n, uint32_t k, const uint32_t* __restrict__ combo,
+                          const CjTerm* __restrict__ terms, unsigned long long* count, uint64_t* nch,
+                          uint64_t* drows, uint32_t* plan) {
+  for (uint64_t c = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; c < n; c += (uint64_t)gridDim.x * blockDim.x) {
+    uint64_t len1 = ~0ull, len2 = ~0ull;
+    uint32_t best1 = 0, best2 = 0, n1 = 0, n2 = 0;
+    bool empty = false;
+    for (uint32_t j = 0; j < k; ++j) {
+      const CjTerm& t = terms[combo[c * k + j]];
+      const uint64_t len = t.hi - t.lo;
+      empty |= len == 0;
+      if (t.nvars == 2) {
+        ++n2;
+        if (len < len2) { len2 = len; best2 = j; }
+      } else {
+        ++n1;
+        if (len < len1) { len1 = len; best1 = j; }
+      }
+    }
+    uint64_t rows = 0;
+    uint32_t p = 0;
+    if (!empty) {
+      if (!n2) { rows = len1; p = kCjAllOne | best1 << 2; }
+      else if (n1 && len1 < len2) { rows = len1; p = kCjDriveOne | best1 << 2 | best2 << 4 | (n2 > 1 ? 64u : 0u); }
+      else { rows = len2; p = kCjDriveTwo | best2 << 2; }
+    }
+    count[c] = 0;
+    nch[c] = (rows + kCjChunk - 1) / kCjChunk;
+    drows[c] = rows;
+    plan[c] = p;
+  }
+}
+
+// first row of [lo, hi) with (c0, c1) >= key = c0 << 32 | c1 (rows ascending by (c0, c1))
+__device__ __forceinline__ uint64_t lower_pair(const uint32_t* c0, const uint32_t* c1, uint64_t lo, uint64_t hi,
+                                               uint64_t key) {
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if ((((uint64_t)c0[mid] << 32) | c1[mid]) < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+// is x a V1 of the one-variable term t
+__device__ __forceinline__ bool cj_has1(const CjTerm& t, uint32_t x) {
+  if (t.fcol) {
+    const uint64_t r = lower_pair(t.v1, t.fcol, t.lo, t.hi, ((uint64_t)x << 32) | t.fval);
+    return r < t.hi && t.v1[r] == x && t.fcol[r] == t.fval;
+  }
+  const uint64_t r = lower_row(t.v1, t.lo, t.hi, x);
+  return r < t.hi && t.v1[r] == x;
+}
+// is (x, y) a (V1, V2) of the two-variable term t
+__device__ __forceinline__ bool cj_has2(const CjTerm& t, uint32_t x, uint32_t y) {
+  const uint64_t r = lower_pair(t.v1, t.v2, t.lo, t.hi, ((uint64_t)x << 32) | y);
+  return r < t.hi && t.v1[r] == x && t.v2[r] == y;
+}
+
+// choff: exclusive scan of nch.  One wave per chunk of a combination's driver.
+__global__ void __launch_bounds__(kB) k_cj_count(uint32_t n, uint32_t k, const uint64_t* __restrict__ choff,
+                                                const uint64_t* __restrict__ nch,
+                                                const uint32_t* __restrict__ combo,
+                                                const uint32_t* __restrict__ plan,
+                                                const CjTerm* __restrict__ terms, unsigned long long* count) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t total = choff[n - 1] + nch[n - 1];
+  const uint64_t nwaves = (uint64_t)gridDim.x * (kB / 64);
+  for (uint64_t ch = (uint64_t)blockIdx.x * (kB / 64) + (threadIdx.x >> 6); ch < total; ch += nwaves) {
+    uint32_t a = 0, b = n;                     // the last combination with choff <= ch owns the chunk
+    while (a < b) {
+      const uint32_t mid = a + ((b - a) >> 1);
+      if (choff[mid] <= ch) a = mid + 1; else b = mid;
+    }
+    const uint32_t i = __builtin_amdgcn_readfirstlane(a - 1);     // one owner per wave: its records are scalar loads
+    const uint32_t pl = plan[i];
+    const uint32_t mode = pl & 3u, drv = (pl >> 2) & 3u, sel2 = (pl >> 4) & 3u;
+    const bool several2 = (pl & 64u) != 0;
+    CjTerm T[4];
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) T[j] = terms[combo[(uint64_t)i * k + (j < k ? j : 0u)]];
+    CjTerm D = T[0], S = T[0];
+#pragma unroll
+    for (uint32_t j = 1; j < 4; ++j) {
+      if (j == drv) D = T[j];
+      if (j == sel2) S = T[j];
+    }
+    const uint64_t r0 = D.lo + (ch - choff[i]) * kCjChunk;
+    const uint64_t r1 = min(r0 + kCjChunk, D.hi);
+    unsigned long long cnt = 0;
+    for (uint64_t base = r0; base < r1; base += 64) {
+      const uint64_t r = base + lane;
+      bool ok = r < r1;
+      if (ok && D.fcol) ok = D.fcol[r] == D.fval;
+      uint32_t x = 0, y = 0;
+      if (ok) {
+        x = D.v1[r];
+        if (D.nvars == 2) y = D.v2[r];
+      }
+#pragma unroll
+      for (uint32_t j = 0; j < 4; ++j) {
+        if (j >= k || j == drv || !ok) continue;
+        if (T[j].nvars == 1) ok = cj_has1(T[j], x);
+        else if (mode == kCjDriveTwo) ok = cj_has2(T[j], x, y);
+      }
+      if (mode != kCjDriveOne) {
+        cnt += ok ? 1u : 0u;
+        continue;
+      }
+      uint64_t sa = 0, sb = 0;                 // x's rows in the smallest two-variable term
+      if (ok) {
+        sa = lower_row(S.v1, S.lo, S.hi, x);
+        sb = lower_row(S.v1, sa, S.hi, (uint64_t)x + 1);
+      }
+      if (!several2) {
+        cnt += sb - sa;
+        continue;
+      }
+      const bool wide = sb - sa > kCjCoop;
+      if (!wide) {
+        for (uint64_t q = sa; q < sb; ++q) {
+          const uint32_t yq = S.v2[q];
+          bool in = true;
+#pragma unroll
+          for (uint32_t j = 0; j < 4; ++j)
+            if (j < k && j != sel2 && T[j].nvars == 2 && in) in = cj_has2(T[j], x, yq);
+          cnt += in ? 1u : 0u;
+        }
+      }
+      // a hub's sub-range: the whole wave walks it, one such lane at a time
+      uint64_t todo = __ballot(wide);
+      while (todo) {
+        const int leader = __ffsll((unsigned long long)todo) - 1;
+        todo &= todo - 1;
+        const uint32_t xl = __shfl(x, leader, 64);
+        const uint64_t qa = __shfl(sa, leader, 64), qb = __shfl(sb, leader, 64);
+        for (uint64_t q = qa + lane; q < qb; q += 64) {
+          const uint32_t yq = S.v2[q];
+          bool in = true;
+#pragma unroll
+          for (uint32_t j = 0; j < 4; ++j)
+            if (j < k && j != sel2 && T[j].nvars == 2 && in) in = cj_has2(T[j], xl, yq);
+          cnt += in ? 1u : 0u;
+        }
+      }
+    }
+    cnt = wave_reduce_sum(cnt);
+    if (lane == 0 && cnt) atomicAdd(&count[i], cnt);
+  }
+}
+
+}  // namespace
+
+void conjunction_counts(Ctx& c, const uint32_t* tpl, uint64_t m, const uint32_t* combo, uint64_t n, uint32_t k,
+                        uint64_t* counts) {
+  DAS_CHECK(k >= 2 && k <= 4, DAS_E_INVALID, "conjunction counts: k outside 2..4");
+  miner_check(c);
+  const Index& idx = c.idx;
+  DAS_CHECK((tpl || !m) && (combo || !n) && (counts || !n), DAS_E_INVALID, "conjunction counts: null argument");
+  DAS_CHECK(m < (1ull << 32) && n < (1ull << 32), DAS_E_UNSUPPORTED, "conjunction counts: too many rows in one call");
+  const uint32_t unord[2] = {type_named(idx, "Similarity"), type_named(idx, "Set")};
+  for (uint64_t i = 0; i < m; ++i) {
+    const uint32_t ar = tpl[i], ty = tpl[m + i];
+    DAS_CHECK(ar == 2 || ar == 3, DAS_E_INVALID, "conjunction counts: a template of arity other than 2 or 3");
+    DAS_CHECK(ty < idx.n_types, DAS_E_INVALID, "conjunction counts: type id out of range");
+    DAS_CHECK(ty != unord[0] && ty != unord[1], DAS_E_UNSUPPORTED,
+              "conjunction counts: Similarity / Set templates take the per-query path");
+    uint32_t ng = 0;
+    for (uint32_t p = 0; p < ar; ++p) {
+      const uint32_t t = tpl[(2 + p) * m + i];
+      if (t == kNone) continue;
+      DAS_CHECK(t < idx.n_atoms, DAS_E_INVALID, "conjunction counts: grounded target out of range");
+      ++ng;
+    }
+    DAS_CHECK(ng >= 1 && ng < ar, DAS_E_INVALID, "conjunction counts: a template needs a wildcard and a grounded target");
+  }
+  for (uint64_t i = 0; i < n * k; ++i)
+    DAS_CHECK(combo[i] < m, DAS_E_INVALID, "conjunction counts: template index out of range");
+  if (!n) return;
+  hipStream_t s = c.s;
+  DBuf<uint32_t> d_tpl(5 * m, s), d_combo(n * k, s), plan(n, s);
+  DBuf<CjTerm> terms(m, s);
+  DBuf<unsigned long long> count(n, s);
+  DBuf<uint64_t> ch(3 * n, s);                        // nch, choff, driver rows
+  DBuf<uint8_t> blocked;
+  upload_blocked(c, blocked);
+  DAS_HIP(hipMemcpyAsync(d_tpl.p, tpl, 20 * m, hipMemcpyHostToDevice, s));
+  DAS_HIP(hipMemcpyAsync(d_combo.p, combo, 4 * n * k, hipMemcpyHostToDevice, s));
+  PcIndex X{};
+  for (int p = 0; p < 2; ++p) X.p2[p] = view_of(idx.pidx[2][p], 2);
+  for (int p = 0; p < 3; ++p) X.p3[p] = view_of(idx.pidx[3][p], 3);
+  {
+    // per template: its row, ~2 key searches and an equal range -- a rough bound of 3 searches of
+    // 24 steps, every step taken as an 8-byte ukey word (an equal range's steps read 4-byte column
+    // words) -- and the descriptor
+    ProfScope ps(c, "k_cj_resolve", m * (20.0 + 3.0 * 8.0 * 24.0 + sizeof(CjTerm)));
+    hipLaunchKernelGGL(k_cj_resolve, G(m), dim3(kB), 0, s, m, (const uint32_t*)d_tpl.p,
+                       (const uint32_t*)(d_tpl.p + m), (const uint32_t*)(d_tpl.p + 2 * m),
+                       (const uint32_t*)(d_tpl.p + 3 * m), (const uint32_t*)(d_tpl.p + 4 * m), X,
+                       (const uint8_t*)blocked.p, terms.p);
+    DAS_HIP(hipGetLastError());
+  }
+  {
+    ProfScope ps(c, "k_cj_plan", n * (k * (4.0 + 24.0) + 28.0));
+    hipLaunchKernelGGL(k_cj_plan, G(n), dim3(kB), 0, s, n, k, (const uint32_t*)d_combo.p, (const CjTerm*)terms.p,
+                       count.p, ch.p, ch.p + 2 * n, plan.p);
+    DAS_HIP(hipGetLastError());
+  }
+  exclusive_scan<uint64_t>(ch.p, n, ch.p + n, s);
+  {
+    // The scope counts the combinations' records; the driver rows walked are
+    // known on the device only and are added below when profiling is on.  The
+    // probes (~log2(range) dependent loads per row and other term, through
+    // L2 / MALL) are not bytes of a stream and are not counted: the kernel
+    // is bound by their latency, not by HBM.
+    ProfScope ps(c, "k_cj_count", n * (16.0 + 4.0 + k * (4.0 + sizeof(CjTerm)) + 8.0));
+    hipLaunchKernelGGL(k_cj_count, dim3(2048), dim3(kB), 0, s, (uint32_t)n, k, (const uint64_t*)(ch.p + n),
+                       (const uint64_t*)ch.p, (const uint32_t*)d_combo.p, (const uint32_t*)plan.p,
+                       (const CjTerm*)terms.p, count.p);
+    DAS_HIP(hipGetLastError());
+  }
+  if (c.prof) {                                        // (profiling only: the driver rows, summed on the device)
+    DBuf<uint64_t> acc(n + 1, s);
+    prof_add_bytes(c, "k_cj_count", 4.0 * scan_total<uint64_t>(SpanIn<uint64_t>{ch.p + 2 * n}, n, acc.p, s));
+  }
+  DAS_HIP(hipMemcpyAsync(counts, count.p, 8 * n, hipMemcpyDeviceToHost, s));
+  DAS_HIP(hipStreamSynchronize(s));
+  count_readback();
 }
 
 }  // namespace das

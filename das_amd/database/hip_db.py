@@ -178,6 +178,7 @@ class HipDB(RelationalDB):
         self._name_dfas = {}            # (pattern, ascii_only) -> NameDFA or None
         self.name_search_stats = {"device": 0, "host": 0}   # get_matched_node_name calls answered by each path
         self.miner_stats = {"device": 0, "host": 0}         # halo / pattern_counts calls answered by each path
+        self.conjunction_stats = {"device": 0, "host": 0}   # conjunction_counts: combinations counted by each path
 
     def __repr__(self):
         return "<HipDB>"
@@ -747,6 +748,41 @@ class HipDB(RelationalDB):
         self.miner_stats["device"] += 1
         count = cols[5].astype(np.uint64) | (cols[6].astype(np.uint64) << np.uint64(32))
         return _miner.PatternCounts(self, cols[0].copy(), cols[1].copy(), np.ascontiguousarray(cols[2:5].T), count)
+
+    def conjunction_counts(self, pc, combos):
+        """The mining loop's compute_count of And-combinations of templates:
+        `combos` is an (n, k) integer array (or a list of equal-length
+        tuples) of row indices into the PatternCounts `pc`, 2 <= k <= 4, an
+        index may repeat; returns np.uint64[n] in input order, 0 where
+        matched() is false.  Combinations of ordered templates are counted
+        in one das_conjunction_counts call (index rows walked and probed, no
+        join output).  The per-query loop miner.conjunction_counts_host
+        counts the rest: a combination holding a Similarity / Set template,
+        and every combination with DAS_MINER=0, CONFIG['no_overload'], stale
+        pattern entries, a shard of several or a `pc` without this DB's atom
+        ids.  `conjunction_stats` counts the combinations of each path."""
+        from ..pattern_matcher.pattern_matcher import CONFIG
+        combos = _miner.check_combos(combos, len(pc))
+        out = np.zeros(len(combos), dtype=np.uint64)
+        on_host = np.ones(len(combos), dtype=bool)
+        if (self._miner_on_device() and not CONFIG['no_overload'] and pc.db is self and pc.type_id is not None
+                and len(combos)):
+            unordered = [self.type_id[t] for t in UNORDERED_LINK_TYPES if t in self.type_id]
+            on_host = np.isin(pc.type_id, unordered)[combos].any(axis=1)
+        dev = ~on_host
+        if dev.any():
+            used, local = np.unique(combos[dev], return_inverse=True)       # only the templates it needs
+            tpl = np.vstack([pc.arity[used], pc.type_id[used], pc.targets[used].T])
+            out[dev] = self.ctx.conjunction_counts(tpl, local.reshape(-1, combos.shape[1]))
+            self.conjunction_stats["device"] += int(dev.sum())
+        if on_host.any():
+            out[on_host] = _miner.conjunction_counts_host(self, pc, combos[on_host])
+            self.conjunction_stats["host"] += int(on_host.sum())
+        return out
+
+    def isurprisingness(self, pc, combos, universe_size, normalized=False):
+        """miner.isurprisingness over this DB."""
+        return _miner.isurprisingness(self, pc, combos, universe_size, normalized)
 
     def get_matched_node_name(self, node_type: str, substring: str) -> str:
         """redis_mongo_db.py:287-293 (Mongo $regex on names of that type).

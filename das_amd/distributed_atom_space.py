@@ -11,6 +11,8 @@ import os
 from enum import Enum, auto
 from typing import Dict, List, Tuple, Union
 
+import numpy as np
+
 from . import _lib
 from . import loader as _loader
 from .database.db_interface import WILDCARD
@@ -239,6 +241,22 @@ class DistributedAtomSpace:
             return self.db.pattern_counts(links)
         from . import miner
         return miner.pattern_counts_host(self.db, links)
+
+    def conjunction_counts(self, pc, combos):
+        """compute_count of And-combinations of the templates of `pc` (rows
+        of 2 to 4 indices into it): np.uint64 per combination.  On a HipDB
+        one device call for the ordered templates; any other DBInterface runs
+        one matched() per combination (miner.conjunction_counts_host)."""
+        if hasattr(self.db, "conjunction_counts"):
+            return self.db.conjunction_counts(pc, combos)
+        from . import miner
+        return np.asarray(miner.conjunction_counts_host(self.db, pc, combos))
+
+    def isurprisingness(self, pc, combos, universe_size, normalized=False):
+        """Count and compute_isurprisingness of every combination: an object
+        with `.count` and `.value` (miner.isurprisingness)."""
+        from . import miner
+        return miner.isurprisingness(self, pc, combos, universe_size, normalized)
 
     def query(self, query: LogicalExpression, output_format: QueryOutputFormat = QueryOutputFormat.HANDLE) -> str:
         """distributed_atom_space.py:298-321"""

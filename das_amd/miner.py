@@ -1,4 +1,4 @@
-"""The two bulk steps of notebooks/SimplePatternMiner.ipynb.
+"""The bulk steps of notebooks/SimplePatternMiner.ipynb.
 
 `halo` is the notebook's cell 6: around a set of seed atoms, level by level,
 every link of arity 2 or 3 that holds a frontier atom (the five '*'-typed
@@ -15,7 +15,14 @@ had to write before, kept as the definition of the answer and as the path of
 `HipDB.halo` / `HipDB.pattern_counts` answer from the resident index instead
 (das_halo_expand, das_pattern_counts): one pass over the frontier's incoming
 lists per level, one key-range width or equal range per template.
+
+The mining loop (cells c34c1d24 / efac9ac6) is the third step:
+`conjunction_counts_host` is its compute_count per And-combination of
+templates, `HipDB.conjunction_counts` counts a batch of them from the index
+(das_conjunction_counts) and `isurprisingness` adds the notebook's score, the
+sub-combinations it needs counted once per batch.
 """
+import itertools
 import time
 
 import numpy as np
@@ -318,3 +325,192 @@ def pattern_counts_host(db, links, budget_s=None):
                             np.array([counts[k] for k in keys], dtype=np.uint64), [list(k) for k in keys])
     out.stopped = stopped
     return out
+
+
+# ---------------------------------------------------------------------------
+# the mining loop (cells c34c1d24 / efac9ac6): counts of And-combinations of
+# templates and their I-surprisingness
+# ---------------------------------------------------------------------------
+
+def check_combos(combos, m):
+    """`combos` as an (n, k) uint32 array of row indices into a PatternCounts
+    of m templates.  ValueError: k outside 2..4, rows of unequal length, an
+    index that is negative or >= m."""
+    try:
+        a = np.asarray(combos if isinstance(combos, np.ndarray) else list(combos))
+    except ValueError as e:                       # numpy refuses ragged rows
+        raise ValueError("conjunction counts: combinations of unequal length") from e
+    if a.dtype == object:
+        raise ValueError("conjunction counts: combinations of unequal length")
+    if a.ndim == 1 and a.size == 0:               # no combination at all
+        a = np.zeros((0, 2), dtype=np.int64)
+    if a.ndim != 2 or not 2 <= a.shape[1] <= 4:
+        raise ValueError("conjunction counts: combinations are rows of 2 to 4 template indices")
+    if a.dtype.kind not in "iu":
+        raise ValueError("conjunction counts: template indices are integers")
+    a = a.astype(np.int64)
+    if a.size and (a.min() < 0 or a.max() >= m):
+        raise ValueError("conjunction counts: template index out of range")
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def build_composite_pattern(terms):
+    """The notebook's fold: And([And([t0, t1]), t2]) ..."""
+    from .pattern_matcher.pattern_matcher import And
+    assert len(terms) > 1
+    first = terms[0]
+    for second in terms[1:]:
+        first = And([first, second])
+    return first
+
+
+class HostCounts(np.ndarray):
+    """conjunction_counts_host's counts; `.stopped` = {done, of} if its time
+    budget ran out (the rows from `done` on are then 0)."""
+    stopped = None
+
+
+def conjunction_counts_host(db, pc, combos, budget_s=None):
+    """compute_count(build_composite_pattern([pc.pattern(i) for i in combo]))
+    per combination: one matched() each, answer.count() rows, 0 where it is
+    false.  The definition of the answer, and the path of DAS_MINER=0, of a
+    DB with stale pattern entries, of CONFIG['no_overload'], of Similarity /
+    Set templates and of any DB without atom ids.  budget_s: stop after that
+    many seconds (`.stopped`; measurement tools only)."""
+    from .pattern_matcher.pattern_matcher import PatternMatchingAnswer
+    combos = check_combos(combos, len(pc))
+    out = np.zeros(len(combos), dtype=np.uint64).view(HostCounts)
+    patterns = {}
+    t0 = time.perf_counter()
+    for c, combo in enumerate(combos.tolist()):
+        if budget_s is not None and time.perf_counter() - t0 > budget_s:
+            out.stopped = {"done": c, "of": len(combos)}
+            break
+        for i in combo:
+            if i not in patterns:
+                patterns[i] = pc.pattern(i)
+        answer = PatternMatchingAnswer()
+        if build_composite_pattern([patterns[i] for i in combo]).matched(db, answer):
+            out[c] = answer.count()
+    return out
+
+
+_SUBSETS = {k: {s: list(itertools.combinations(range(k), s)) for s in range(2, k)} for k in (2, 3, 4)}
+
+
+def sub_combinations(combos):
+    """The proper sub-combinations compute_isurprisingness counts, merged
+    over the batch: {size: (distinct, where)} with `distinct` the (u, size)
+    sorted index rows, each once, and where[c, j] the row of `distinct` that
+    is subset j of combination c, the subsets in itertools.combinations order
+    of the positions.  k = 2: none; 3: the three pairs; 4: six pairs and four
+    triples.  An index twice in a combination stays twice in its subsets."""
+    combos = np.asarray(combos)
+    n, k = combos.shape
+    out = {}
+    for size, subsets in _SUBSETS[k].items():
+        rows = np.sort(np.stack([combos[:, list(s)] for s in subsets], axis=1).reshape(n * len(subsets), size), axis=1)
+        if len(rows):
+            distinct, where = np.unique(rows, axis=0, return_inverse=True)
+        else:
+            distinct, where = rows, np.zeros(0, dtype=np.int64)
+        out[size] = (distinct.astype(np.uint32), where.reshape(n, len(subsets)))
+    return out
+
+
+def isurprisingness_from_counts(count, term_counts, universe_size, pair_counts=None, triple_counts=None,
+                                normalized=False):
+    """compute_isurprisingness over arrays, in float64 and in the notebook's
+    order of operations.  count: (n,) the combinations' counts; term_counts:
+    (n, k) the terms' own counts; pair_counts: (n, C(k, 2)) the counts of the
+    pairs (0,1) (0,2) .. in itertools.combinations order (k >= 3);
+    triple_counts: (n, 4) of (0,1,2) (0,1,3) (0,2,3) (1,2,3) (k = 4), as
+    the notebook counts them: with a flat three-term And (`flat_triple_counts`).
+    normalized divides by prob(count): where the count is 0 the notebook
+    raises ZeroDivisionError; the value here is nan."""
+    u = float(universe_size)
+
+    def prob(x):
+        return np.asarray(x, dtype=np.float64) / u
+
+    t = prob(term_counts)
+    k = t.shape[1]
+    if k == 2:
+        subset_probs = [t[:, 0] * t[:, 1]]
+    elif k == 3:
+        p = prob(pair_counts)                       # (0,1) (0,2) (1,2)
+        subset_probs = [t[:, 0] * t[:, 1] * t[:, 2], p[:, 0] * t[:, 2], p[:, 1] * t[:, 1], p[:, 2] * t[:, 0]]
+    elif k == 4:
+        p = prob(pair_counts)                       # (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)
+        q = prob(triple_counts)                     # (0,1,2) (0,1,3) (0,2,3) (1,2,3)
+        subset_probs = [t[:, 0] * t[:, 1] * t[:, 2] * t[:, 3], p[:, 0] * p[:, 5], p[:, 1] * p[:, 4],
+                        p[:, 2] * p[:, 3], q[:, 0] * t[:, 3], q[:, 1] * t[:, 2], q[:, 2] * t[:, 1], q[:, 3] * t[:, 0]]
+    else:
+        raise NotImplementedError()
+    sp = np.stack(subset_probs, axis=1)
+    pc = prob(count)
+    value = np.maximum(pc - sp.max(axis=1), sp.min(axis=1) - pc)
+    if normalized:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            value = np.where(pc > 0, value / pc, np.nan)
+    return value
+
+
+def flat_triple_counts(term_counts, pair_counts, triple_counts):
+    """The four triples of a 4-combination as compute_isurprisingness counts
+    them.  It asks `And([ti, tj, tl])`, one flat And, not the nested fold of
+    build_composite_pattern, and the reference's And starts over from the
+    next term once its running join is empty (pattern_matcher.py:717-729):
+    false, count 0, if a term has no rows; the third term's own count if the
+    first two join to nothing; else the size of the join of the three.  The
+    order of the terms matters, so this is derived per combination from
+    counts that do not depend on it: term_counts (n, 4), pair_counts (n, 6)
+    and triple_counts (n, 4), the join sizes in itertools.combinations order
+    of the positions."""
+    t = np.asarray(term_counts, dtype=np.uint64)
+    p = np.asarray(pair_counts, dtype=np.uint64)
+    out = np.array(triple_counts, dtype=np.uint64)
+    pairs = _SUBSETS[4][2]
+    for j, (a, b, c) in enumerate(_SUBSETS[4][3]):
+        restart = p[:, pairs.index((a, b))] == 0
+        out[restart, j] = t[restart, c]
+        out[(t[:, a] == 0) | (t[:, b] == 0) | (t[:, c] == 0), j] = 0
+    return out
+
+
+class ISurprisingness:
+    """`.count` (uint64) and `.value` (float64) per combination."""
+
+    def __init__(self, count, value):
+        self.count = count
+        self.value = value
+
+    def __len__(self):
+        return len(self.count)
+
+
+def isurprisingness(db, pc, combos, universe_size, normalized=False):
+    """The mining loop's count and compute_isurprisingness of every
+    combination (rows of 2 to 4 indices into `pc`): the combinations and
+    their merged sub-combinations (`sub_combinations`) are counted with one
+    conjunction_counts call per size, the terms' own counts are pc.count.
+    The notebook counts the triples of a 4-combination with a flat And,
+    which is not the join of the three where the first two join to nothing:
+    `flat_triple_counts` turns the join sizes into what it gets.
+    normalized=True with count 0 gives nan (the notebook divides by zero)."""
+    combos = check_combos(combos, len(pc))
+
+    def counts_of(rows):
+        if hasattr(db, "conjunction_counts"):
+            return np.asarray(db.conjunction_counts(pc, rows), dtype=np.uint64)
+        return np.asarray(conjunction_counts_host(db, pc, rows), dtype=np.uint64)
+
+    count = counts_of(combos)
+    sub = {}
+    for size, (distinct, where) in sub_combinations(combos).items():
+        sub[size] = counts_of(distinct)[where] if len(distinct) else np.zeros(where.shape, dtype=np.uint64)
+    terms = np.asarray(pc.count)[combos.astype(np.int64)]
+    if 3 in sub:
+        sub[3] = flat_triple_counts(terms, sub[2], sub[3])
+    value = isurprisingness_from_counts(count, terms, universe_size, sub.get(2), sub.get(3), normalized)
+    return ISurprisingness(count, value)

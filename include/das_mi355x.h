@@ -276,6 +276,27 @@ int das_halo_expand(das_ctx_t* ctx, const uint32_t* seed_ids, uint64_t n_seeds, 
  * das_halo_expand (a host link id >= n_atoms: DAS_ERR_INVALID). */
 int das_pattern_counts(das_ctx_t* ctx, const das_table_t* links, const uint32_t* link_ids, uint64_t n,
                        das_table_t** out);
+#define DAS_CJ_CHUNK_ROWS 1024      /* driver rows one wave counts per step */
+/* The mining loop's compute_count (notebook cells c34c1d24 / efac9ac6) of n
+ * And-combinations of k templates each, 2 <= k <= 4.  `tpl`: m templates as
+ * das_pattern_counts reports them, column-major 5 x m: arity, type id, t0, t1,
+ * t2 (DAS_NONE = wildcard or unused).  `combo`: row-major n x k indices into
+ * tpl (an index may repeat).  A template binds V1, or V1 and V2, at its
+ * wildcards in position order (build_pattern_from_template), so counts[c] =
+ * the rows of the natural join of the combination's terms on those names: 0
+ * if a term has no rows (no such key, a black-listed type); with one-variable
+ * terms only, the atoms in every term's V1 set; otherwise the (V1, V2) pairs
+ * of every two-variable term whose V1 is in every one-variable term (V1 == V2
+ * on a row counts).  No join output: the smallest suitable term's rows in
+ * P_{a,p} are walked and the other terms probed by binary search; three
+ * launches, one scan and one read-back of the n counts.  k outside 2..4, an
+ * index >= m, an arity other than 2 or 3, a template without a wildcard or
+ * without a grounded target, a type id >= n_types or a grounded id >= n_atoms:
+ * DAS_ERR_INVALID; a Similarity / Set template: DAS_ERR_UNSUPPORTED; no index:
+ * DAS_ERR_NOT_BUILT; a sharded index with world > 1: DAS_ERR_UNSUPPORTED --
+ * each before anything is launched.  n == 0: DAS_OK, nothing launched. */
+int das_conjunction_counts(das_ctx_t* ctx, const uint32_t* tpl, uint64_t m, const uint32_t* combo, uint64_t n,
+                           uint32_t k, uint64_t* counts);
 
 /* ---- query operators ----------------------------------------------------- */
 /* One Link with >= 1 wildcard, evaluated against the pattern index
