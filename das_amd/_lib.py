@@ -19,6 +19,7 @@ TABLE_COMPOSITE = 2
 
 ERR_INVALID, ERR_HIP, ERR_NOT_BUILT, ERR_UNSUPPORTED, ERR_INTERNAL, ERR_ATTRIBUTE = -1, -2, -3, -4, -5, -6
 ERR_SYNTAX = -7
+ERR_LIMIT = -8                    # DAS_ERR_LIMIT: more work than the caller's limit allows -> ValueError
 
 
 class DasNativeError(RuntimeError):
@@ -81,6 +82,8 @@ HALO_MAX_LEVELS = 8               # DAS_HALO_MAX_LEVELS
 HALO_BLOCK_ENTRIES = 1024         # DAS_HALO_BLOCK_ENTRIES: incoming-list entries one workgroup marks per pass
 PC_CHUNK_ROWS = 1024              # DAS_PC_CHUNK_ROWS: index rows one wave counts per step of a (1,2)-grounded template
 CJ_CHUNK_ROWS = 1024              # DAS_CJ_CHUNK_ROWS: driver rows one wave counts per step of a conjunction
+MX_TILE = 1 << 20                 # DAS_MX_TILE: combinations of one tile of the exhaustive search
+MX_MAX_TOP = 65536                # DAS_MX_MAX_TOP: rows das_mine_combinations returns at most
 
 
 class das_plan_node_t(C.Structure):
@@ -128,6 +131,8 @@ _SIGS = {
     "das_halo_expand": (C.c_int, [P, P, C.c_uint64, C.c_uint32, P, P]),
     "das_pattern_counts": (C.c_int, [P, P, P, C.c_uint64, C.POINTER(P)]),
     "das_conjunction_counts": (C.c_int, [P, P, C.c_uint64, P, C.c_uint64, C.c_uint32, P]),
+    "das_mine_combinations": (C.c_int, [P, P, C.c_uint64, P, P, C.c_uint64, P, C.c_uint64, C.c_uint32, C.c_uint64,
+                                        C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, P, P, P, P, P]),
     "das_export_outgoing": (C.c_int, [P, P, P, P, P]),
     "das_counters": (C.c_int, [P]),
     "das_scan_link": (C.c_int, [P, C.POINTER(das_link_scan_t), C.POINTER(P)]),
@@ -207,7 +212,7 @@ def check(rc, ctx=None):
     if rc != 0:
         msg = lib().das_last_error(ctx)
         msg = msg.decode(errors="replace") if msg else ""
-        if rc == ERR_INVALID:
+        if rc in (ERR_INVALID, ERR_LIMIT):
             raise ValueError(msg)
         if rc == ERR_UNSUPPORTED:
             raise NotImplementedError(msg)
@@ -626,6 +631,37 @@ class Context:
                                            ptr(combos) if combos.size else None, n, k,
                                            ptr(out) if n else None), self.h)
         return out
+
+    def mine_combinations(self, tpl, tpl_count, basics, candidates, k, universe_size, support=0, normalized=False,
+                          top=16, max_combinations=2**32):
+        """The best `top` rows (b, c1[, c2]) of basics x ascending (k - 1)-
+        tuples of candidates by I-surprisingness (das_mine_combinations).
+        tpl: (5, m) uint32 as for conjunction_counts; tpl_count: uint64[m];
+        basics, candidates: indices into tpl.  Returns (combos (r, k) uint32,
+        count uint64[r], value float64[r], (searched, scored, tiles));
+        ValueError, the number in the message, over max_combinations."""
+        tpl = np.ascontiguousarray(np.asarray(tpl, dtype=np.uint32))
+        if tpl.ndim != 2 or tpl.shape[0] != 5:
+            raise ValueError("mine: templates are a 5 x m array")
+        cnt = np.ascontiguousarray(np.asarray(tpl_count, dtype=np.uint64).ravel())
+        if cnt.size != tpl.shape[1]:
+            raise ValueError("mine: one count per template")
+        b = np.ascontiguousarray(np.asarray(basics, dtype=np.uint32).ravel())
+        c = np.ascontiguousarray(np.asarray(candidates, dtype=np.uint32).ravel())
+        k, top = int(k), int(top)
+        rows = min(max(top, 1), MX_MAX_TOP)
+        combo = np.zeros((rows, max(k, 1)), dtype=np.uint32)
+        count = np.zeros(rows, dtype=np.uint64)
+        value = np.zeros(rows, dtype=np.float64)
+        n_out = C.c_uint32()
+        stats = np.zeros(3, dtype=np.uint64)
+        check(lib().das_mine_combinations(self.h, ptr(tpl) if tpl.size else None, tpl.shape[1],
+                                          ptr(cnt) if cnt.size else None, ptr(b) if b.size else None, b.size,
+                                          ptr(c) if c.size else None, c.size, k, int(universe_size), int(support),
+                                          1 if normalized else 0, top, int(max_combinations), ptr(combo), ptr(count),
+                                          ptr(value), C.byref(n_out), ptr(stats)), self.h)
+        r = n_out.value
+        return combo[:r].copy(), count[:r].copy(), value[:r].copy(), tuple(int(x) for x in stats)
 
     def ctype_lookup(self, digest):
         d = np.ascontiguousarray(np.asarray(digest, dtype=np.uint32))

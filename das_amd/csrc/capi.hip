@@ -565,6 +565,19 @@ int das_conjunction_counts(das_ctx_t* ctx, const uint32_t* tpl, uint64_t m, cons
   return guarded(ctx, [&] { das::conjunction_counts(ctx->c, tpl, m, combo, n, k, counts); });
 }
 
+int das_mine_combinations(das_ctx_t* ctx, const uint32_t* tpl, uint64_t m, const uint64_t* tpl_count,
+                          const uint32_t* basics, uint64_t n_basics, const uint32_t* candidates, uint64_t n_candidates,
+                          uint32_t k, uint64_t universe_size, uint64_t support, uint32_t normalized, uint32_t top,
+                          uint64_t max_combinations, uint32_t* out_combo, uint64_t* out_count, double* out_value,
+                          uint32_t* n_out, uint64_t stats[3]) {
+  if (!ctx) return fail(ctx, DAS_ERR_INVALID, "null argument");
+  return guarded(ctx, [&] {
+    das::mine_combinations(ctx->c, tpl, m, tpl_count, basics, n_basics, candidates, n_candidates, k, universe_size,
+                           support, normalized != 0, top, max_combinations, out_combo, out_count, out_value, n_out,
+                           stats);
+  });
+}
+
 int das_ctype_lookup(das_ctx_t* ctx, const uint32_t digest[4], int64_t* ctype_id) {
   return guarded(ctx, [&] {
     const auto& v = ctx->c.idx.ctype_digest;

@@ -395,6 +395,15 @@ std::unique_ptr<Table> pattern_counts(Ctx& c, const uint32_t* d_links, uint64_t 
 // t1, t2; kNone = wildcard or unused) on V1 / V2 in wildcard order
 void conjunction_counts(Ctx& c, const uint32_t* tpl, uint64_t m, const uint32_t* combo, uint64_t n, uint32_t k,
                         uint64_t* counts);
+// das_mine_combinations: the best `top` rows (b, c1[, c2]) of basics x ascending
+// (k - 1)-tuples of candidates by I-surprisingness (host arrays in and out);
+// throws DAS_E_LIMIT, stats[0..1] filled, if it would count more than
+// max_combinations
+void mine_combinations(Ctx& c, const uint32_t* tpl, uint64_t m, const uint64_t* tpl_count, const uint32_t* basics,
+                       uint64_t nb, const uint32_t* cands, uint64_t nc, uint32_t k, uint64_t universe_size,
+                       uint64_t support, bool normalized, uint32_t top, uint64_t max_combinations,
+                       uint32_t* out_combo, uint64_t* out_count, double* out_value, uint32_t* n_out,
+                       uint64_t stats[3]);
 
 // Column pointers of a table (kernel argument by value).
 struct ColSet {

@@ -1,8 +1,9 @@
 // SimplePatternMiner's bulk steps on the device (das_halo_expand,
-// das_pattern_counts, das_conjunction_counts): the halo walk of notebook cell
-// 6, the template support counts of build_patterns (cell 5) and the counts of
-// And-combinations of templates the mining loop asks for (at the end of this
-// file).  DESIGN.md §3d.
+// das_pattern_counts, das_conjunction_counts, das_mine_combinations): the halo
+// walk of notebook cell 6, the template support counts of build_patterns (cell
+// 5), the counts of And-combinations of templates the mining loop asks for and
+// the exhaustive search of its last cell (both at the end of this file).
+// DESIGN.md §3d.
 //
 // Halo.  The state is four bitmaps over the atom ids (links seen / links of
 // this level / atoms expanded / atoms of this level).  A level is:
@@ -31,6 +32,7 @@
 
 #include "das_internal.h"
 #include "md5.h"
+#include "mx_unrank.h"
 
 namespace das {
 namespace {
@@ -929,15 +931,8 @@ __global__ void __launch_bounds__(kB) k_cj_count(uint32_t n, uint32_t k, const u
   }
 }
 
-}  // namespace
-
-void conjunction_counts(Ctx& c, const uint32_t* tpl, uint64_t m, const uint32_t* combo, uint64_t n, uint32_t k,
-                        uint64_t* counts) {
-  DAS_CHECK(k >= 2 && k <= 4, DAS_E_INVALID, "conjunction counts: k outside 2..4");
-  miner_check(c);
-  const Index& idx = c.idx;
-  DAS_CHECK((tpl || !m) && (combo || !n) && (counts || !n), DAS_E_INVALID, "conjunction counts: null argument");
-  DAS_CHECK(m < (1ull << 32) && n < (1ull << 32), DAS_E_UNSUPPORTED, "conjunction counts: too many rows in one call");
+// host checks of a batch of templates (column-major arity, type, t0, t1, t2)
+void cj_check_templates(const Index& idx, const uint32_t* tpl, uint64_t m) {
   const uint32_t unord[2] = {type_named(idx, "Similarity"), type_named(idx, "Set")};
   for (uint64_t i = 0; i < m; ++i) {
     const uint32_t ar = tpl[i], ty = tpl[m + i];
@@ -954,36 +949,41 @@ void conjunction_counts(Ctx& c, const uint32_t* tpl, uint64_t m, const uint32_t*
     }
     DAS_CHECK(ng >= 1 && ng < ar, DAS_E_INVALID, "conjunction counts: a template needs a wildcard and a grounded target");
   }
-  for (uint64_t i = 0; i < n * k; ++i)
-    DAS_CHECK(combo[i] < m, DAS_E_INVALID, "conjunction counts: template index out of range");
-  if (!n) return;
+}
+
+// terms[i] = the descriptor of host template i (checked): one upload, one launch
+void cj_resolve(Ctx& c, const uint32_t* tpl, uint64_t m, DBuf<CjTerm>& terms) {
+  const Index& idx = c.idx;
   hipStream_t s = c.s;
-  DBuf<uint32_t> d_tpl(5 * m, s), d_combo(n * k, s), plan(n, s);
-  DBuf<CjTerm> terms(m, s);
-  DBuf<unsigned long long> count(n, s);
-  DBuf<uint64_t> ch(3 * n, s);                        // nch, choff, driver rows
+  terms.alloc(m, s);
+  DBuf<uint32_t> d_tpl(5 * m, s);
   DBuf<uint8_t> blocked;
   upload_blocked(c, blocked);
   DAS_HIP(hipMemcpyAsync(d_tpl.p, tpl, 20 * m, hipMemcpyHostToDevice, s));
-  DAS_HIP(hipMemcpyAsync(d_combo.p, combo, 4 * n * k, hipMemcpyHostToDevice, s));
   PcIndex X{};
   for (int p = 0; p < 2; ++p) X.p2[p] = view_of(idx.pidx[2][p], 2);
   for (int p = 0; p < 3; ++p) X.p3[p] = view_of(idx.pidx[3][p], 3);
-  {
-    // per template: its row, ~2 key searches and an equal range -- a rough bound of 3 searches of
-    // 24 steps, every step taken as an 8-byte ukey word (an equal range's steps read 4-byte column
-    // words) -- and the descriptor
-    ProfScope ps(c, "k_cj_resolve", m * (20.0 + 3.0 * 8.0 * 24.0 + sizeof(CjTerm)));
-    hipLaunchKernelGGL(k_cj_resolve, G(m), dim3(kB), 0, s, m, (const uint32_t*)d_tpl.p,
-                       (const uint32_t*)(d_tpl.p + m), (const uint32_t*)(d_tpl.p + 2 * m),
-                       (const uint32_t*)(d_tpl.p + 3 * m), (const uint32_t*)(d_tpl.p + 4 * m), X,
-                       (const uint8_t*)blocked.p, terms.p);
-    DAS_HIP(hipGetLastError());
-  }
+  // per template: its row, ~2 key searches and an equal range -- a rough bound of 3 searches of
+  // 24 steps, every step taken as an 8-byte ukey word (an equal range's steps read 4-byte column
+  // words) -- and the descriptor
+  ProfScope ps(c, "k_cj_resolve", m * (20.0 + 3.0 * 8.0 * 24.0 + sizeof(CjTerm)));
+  hipLaunchKernelGGL(k_cj_resolve, G(m), dim3(kB), 0, s, m, (const uint32_t*)d_tpl.p,
+                     (const uint32_t*)(d_tpl.p + m), (const uint32_t*)(d_tpl.p + 2 * m),
+                     (const uint32_t*)(d_tpl.p + 3 * m), (const uint32_t*)(d_tpl.p + 4 * m), X,
+                     (const uint8_t*)blocked.p, terms.p);
+  DAS_HIP(hipGetLastError());
+}
+
+// d_count[r] = the count of device row r of d_combo (k indices into terms),
+// 0 < n < 2^32: plan, scan, count; nothing is read back
+void cj_count_rows(Ctx& c, const CjTerm* terms, const uint32_t* d_combo, uint64_t n, uint32_t k,
+                   unsigned long long* d_count) {
+  hipStream_t s = c.s;
+  DBuf<uint32_t> plan(n, s);
+  DBuf<uint64_t> ch(3 * n, s);                        // nch, choff, driver rows
   {
     ProfScope ps(c, "k_cj_plan", n * (k * (4.0 + 24.0) + 28.0));
-    hipLaunchKernelGGL(k_cj_plan, G(n), dim3(kB), 0, s, n, k, (const uint32_t*)d_combo.p, (const CjTerm*)terms.p,
-                       count.p, ch.p, ch.p + 2 * n, plan.p);
+    hipLaunchKernelGGL(k_cj_plan, G(n), dim3(kB), 0, s, n, k, d_combo, terms, d_count, ch.p, ch.p + 2 * n, plan.p);
     DAS_HIP(hipGetLastError());
   }
   exclusive_scan<uint64_t>(ch.p, n, ch.p + n, s);
@@ -995,16 +995,416 @@ void conjunction_counts(Ctx& c, const uint32_t* tpl, uint64_t m, const uint32_t*
     // is bound by their latency, not by HBM.
     ProfScope ps(c, "k_cj_count", n * (16.0 + 4.0 + k * (4.0 + sizeof(CjTerm)) + 8.0));
     hipLaunchKernelGGL(k_cj_count, dim3(2048), dim3(kB), 0, s, (uint32_t)n, k, (const uint64_t*)(ch.p + n),
-                       (const uint64_t*)ch.p, (const uint32_t*)d_combo.p, (const uint32_t*)plan.p,
-                       (const CjTerm*)terms.p, count.p);
+                       (const uint64_t*)ch.p, d_combo, (const uint32_t*)plan.p, terms, d_count);
     DAS_HIP(hipGetLastError());
   }
   if (c.prof) {                                        // (profiling only: the driver rows, summed on the device)
     DBuf<uint64_t> acc(n + 1, s);
     prof_add_bytes(c, "k_cj_count", 4.0 * scan_total<uint64_t>(SpanIn<uint64_t>{ch.p + 2 * n}, n, acc.p, s));
   }
+}
+
+}  // namespace
+
+void conjunction_counts(Ctx& c, const uint32_t* tpl, uint64_t m, const uint32_t* combo, uint64_t n, uint32_t k,
+                        uint64_t* counts) {
+  DAS_CHECK(k >= 2 && k <= 4, DAS_E_INVALID, "conjunction counts: k outside 2..4");
+  miner_check(c);
+  DAS_CHECK((tpl || !m) && (combo || !n) && (counts || !n), DAS_E_INVALID, "conjunction counts: null argument");
+  DAS_CHECK(m < (1ull << 32) && n < (1ull << 32), DAS_E_UNSUPPORTED, "conjunction counts: too many rows in one call");
+  cj_check_templates(c.idx, tpl, m);
+  for (uint64_t i = 0; i < n * k; ++i)
+    DAS_CHECK(combo[i] < m, DAS_E_INVALID, "conjunction counts: template index out of range");
+  if (!n) return;
+  hipStream_t s = c.s;
+  DBuf<uint32_t> d_combo(n * k, s);
+  DBuf<CjTerm> terms;
+  DBuf<unsigned long long> count(n, s);
+  DAS_HIP(hipMemcpyAsync(d_combo.p, combo, 4 * n * k, hipMemcpyHostToDevice, s));
+  cj_resolve(c, tpl, m, terms);
+  cj_count_rows(c, terms.p, d_combo.p, n, k, count.p);
   DAS_HIP(hipMemcpyAsync(counts, count.p, 8 * n, hipMemcpyDeviceToHost, s));
   DAS_HIP(hipStreamSynchronize(s));
+  count_readback();
+}
+
+// ---------------------------------------------------------------------------
+// exhaustive search (das_mine_combinations): the notebook's last cell (efac9ac6)
+// for ngram 2 and 3 -- every basic with every ascending (k - 1)-tuple of
+// candidates, counted, scored (compute_isurprisingness) and cut to the best
+// `top`, without a combination crossing the bus.  DESIGN.md §3d.
+//   pair matrix  count(b, c) of every basic x candidate, rows made on the device
+//   partners     per basic the candidates with count > 0 (not b itself), in
+//                order, each with its pair count; one read-back of the sizes
+//   tiles        DAS_MX_TILE ranks of sum_b C(|S_b|, 2): rank -> (b, i, j)
+//                (mx_unrank.h), the triples and their (i, j) pairs counted by
+//                the plan / scan / count above, scored, the survivors
+//                compacted in rank order behind the running top rows, and the
+//                lot stable-sorted by value, descending, and cut
+// A triple outside the partner lists has a pair count of 0 and so the value 0
+// (or nan): it cannot be reported.  k = 2 scores the pair matrix itself.
+// ---------------------------------------------------------------------------
+namespace {
+
+__global__ void k_mx_pair_rows(uint64_t r0, uint64_t n, uint64_t nc, const uint32_t* __restrict__ basics,
+                               const uint32_t* __restrict__ cands, uint32_t* combo) {
+  for (uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; t < n; t += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t r = r0 + t;
+    combo[2 * t] = basics[r / nc];
+    combo[2 * t + 1] = cands[r % nc];
+  }
+}
+
+// 1: candidate r % nc is a partner of basic r / nc
+struct MxPartnerIn {
+  const unsigned long long* pcount;
+  const uint32_t* basics;
+  const uint32_t* cands;
+  uint64_t nc;
+  __device__ __forceinline__ uint32_t operator()(uint64_t r) const {
+    return pcount[r] > 0 && cands[r % nc] != basics[r / nc] ? 1u : 0u;
+  }
+  static std::string name() { return "MxPartnerIn"; }
+};
+
+// pos: exclusive scan of the partner flags over the n2 = nb * nc matrix rows.
+// part_tpl / part_cnt: the partners of basic 0, of basic 1, .. in candidate
+// order; s_off[b] = where basic b's begin, s_off[nb] = their number.
+__global__ void k_mx_partners(uint64_t n2, uint64_t nb, MxPartnerIn in, const uint32_t* __restrict__ pos,
+                              uint32_t* part_tpl, unsigned long long* part_cnt, uint64_t* s_off) {
+  for (uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; r < n2; r += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t f = in(r), o = pos[r];
+    if (f) {
+      part_tpl[o] = in.cands[r % in.nc];
+      part_cnt[o] = in.pcount[r];
+    }
+    if (r % in.nc == 0) s_off[r / in.nc] = o;
+    if (r == n2 - 1) s_off[nb] = (uint64_t)o + f;
+  }
+}
+
+// Ranks [g0, g0 + n) -> rows: pre[b] = the triangles of the basics before b
+// (pre[nb] = all), so the last b with pre[b] <= g owns rank g.
+// aux: where the row's two partners sit in part_tpl / part_cnt.
+__global__ void k_mx_enum(uint64_t g0, uint64_t n, uint32_t nb, const uint64_t* __restrict__ pre,
+                          const uint64_t* __restrict__ s_off, const uint32_t* __restrict__ basics,
+                          const uint32_t* __restrict__ part_tpl, uint32_t* combo3, uint32_t* combo2, uint32_t* aux) {
+  for (uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; t < n; t += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t g = g0 + t;
+    uint32_t a = 0, e = nb;
+    while (a < e) {
+      const uint32_t mid = a + ((e - a) >> 1);
+      if (pre[mid] <= g) a = mid + 1; else e = mid;
+    }
+    const uint32_t b = a - 1;                          // pre[0] = 0 <= g: a >= 1; pre[b + 1] > g: s >= 2
+    const uint64_t base = s_off[b], s = s_off[b + 1] - base;
+    uint32_t i, j;
+    mx_unrank(g - pre[b], s, i, j);
+    const uint32_t ti = part_tpl[base + i], tj = part_tpl[base + j];
+    combo3[3 * t] = basics[b];
+    combo3[3 * t + 1] = ti;
+    combo3[3 * t + 2] = tj;
+    combo2[2 * t] = ti;
+    combo2[2 * t + 1] = tj;
+    aux[2 * t] = (uint32_t)(base + i);
+    aux[2 * t + 1] = (uint32_t)(base + j);
+  }
+}
+
+// compute_isurprisingness in float64 and in the notebook's order of
+// operations (miner.isurprisingness_from_counts is matched bit for bit): IEEE
+// division and multiplication, each rounded once -- contraction is off for
+// this function, so no product is fused into the subtraction after it.
+__device__ __forceinline__ double mx_value(uint32_t k, double u, unsigned long long c, const unsigned long long tc[3],
+                                           const unsigned long long pc[3], bool normalized) {
+#pragma clang fp contract(off)
+  const double p = (double)c / u;
+  const double t0 = (double)tc[0] / u, t1 = (double)tc[1] / u;
+  double mx, mn;
+  if (k == 2) {
+    mx = mn = t0 * t1;
+  } else {
+    const double t2 = (double)tc[2] / u;
+    const double s0 = (t0 * t1) * t2;
+    const double s1 = ((double)pc[0] / u) * t2;
+    const double s2 = ((double)pc[1] / u) * t1;
+    const double s3 = ((double)pc[2] / u) * t0;
+    mx = fmax(fmax(s0, s1), fmax(s2, s3));
+    mn = fmin(fmin(s0, s1), fmin(s2, s3));
+  }
+  const double hi = p - mx, lo = mn - p;
+  double v = fmax(hi, lo);
+  if (normalized) v = p > 0 ? v / p : __builtin_nan("");
+  return v;
+}
+
+// value[t] and flag[t] (1: reported unless cut) of the tile's n rows.  k = 3:
+// cnt2 = the counts of the (i, j) pairs, aux as k_mx_enum wrote it.
+__global__ void k_mx_score(uint64_t n, uint32_t k, const uint32_t* __restrict__ combo,
+                           const unsigned long long* __restrict__ tcount, const unsigned long long* __restrict__ cnt,
+                           const unsigned long long* __restrict__ cnt2, const uint32_t* __restrict__ aux,
+                           const unsigned long long* __restrict__ part_cnt, double u, unsigned long long support,
+                           uint32_t normalized, double* value, uint32_t* flag) {
+  for (uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; t < n; t += (uint64_t)gridDim.x * blockDim.x) {
+    unsigned long long tc[3] = {0, 0, 0}, pc[3] = {0, 0, 0};
+    bool valid = true;
+    if (k == 2) {
+      const uint32_t b = combo[2 * t], d = combo[2 * t + 1];
+      tc[0] = tcount[b];
+      tc[1] = tcount[d];
+      valid = b != d;                                  // a basic is never inside its own tuple
+    } else {
+      for (uint32_t j = 0; j < 3; ++j) tc[j] = tcount[combo[3 * t + j]];
+      pc[0] = part_cnt[aux[2 * t]];
+      pc[1] = part_cnt[aux[2 * t + 1]];
+      pc[2] = cnt2[t];
+    }
+    const unsigned long long c = cnt[t];
+    const double v = mx_value(k, u, c, tc, pc, normalized != 0);
+    value[t] = v;
+    flag[t] = valid && v > 0 && c >= support ? 1u : 0u;
+  }
+}
+
+// the tile's flagged rows, in rank order, behind the `at` rows kept so far
+__global__ void k_mx_emit(uint64_t n, uint32_t k, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ pos,
+                          const uint32_t* __restrict__ combo, const unsigned long long* __restrict__ cnt,
+                          const double* __restrict__ value, uint64_t at, uint32_t* s_combo, unsigned long long* s_cnt,
+                          double* s_val) {
+  for (uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; t < n; t += (uint64_t)gridDim.x * blockDim.x) {
+    if (!flag[t]) continue;
+    const uint64_t o = at + pos[t];
+    for (uint32_t j = 0; j < k; ++j) s_combo[o * k + j] = combo[t * k + j];
+    s_cnt[o] = cnt[t];
+    s_val[o] = value[t];
+  }
+}
+
+// a positive double orders as its bits: the complement sorts descending
+__global__ void k_mx_keys(uint64_t n, const double* __restrict__ s_val, uint32_t* key_hi, uint32_t* key_lo) {
+  for (uint64_t o = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; o < n; o += (uint64_t)gridDim.x * blockDim.x) {
+    const unsigned long long bits = ~(unsigned long long)__double_as_longlong(s_val[o]);
+    key_hi[o] = (uint32_t)(bits >> 32);
+    key_lo[o] = (uint32_t)bits;
+  }
+}
+
+__global__ void k_mx_take(uint64_t n, uint32_t k, const uint32_t* __restrict__ perm,
+                          const uint32_t* __restrict__ a_combo, const unsigned long long* __restrict__ a_cnt, const double* __restrict__ a_val,
+                          uint32_t* b_combo, unsigned long long* b_cnt, double* b_val) {
+  for (uint64_t o = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; o < n; o += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t r = perm[o];
+    for (uint32_t j = 0; j < k; ++j) b_combo[o * k + j] = a_combo[r * k + j];
+    b_cnt[o] = a_cnt[r];
+    b_val[o] = a_val[r];
+  }
+}
+
+struct MxSel {                                         // kept rows: the running top, then a tile's survivors
+  DBuf<uint32_t> combo;
+  DBuf<unsigned long long> cnt;
+  DBuf<double> val;
+  void alloc(uint64_t rows, uint32_t k, hipStream_t s) {
+    combo.alloc(rows * k, s);
+    cnt.alloc(rows, s);
+    val.alloc(rows, s);
+  }
+};
+
+uint64_t mx_tile() {
+  const long long t = env_int("DAS_MX_TILE", DAS_MX_TILE);
+  return (uint64_t)std::max(1ll, std::min(t, 1ll << 28));
+}
+
+}  // namespace
+
+void mine_combinations(Ctx& c, const uint32_t* tpl, uint64_t m, const uint64_t* tpl_count, const uint32_t* basics,
+                       uint64_t nb, const uint32_t* cands, uint64_t nc, uint32_t k, uint64_t universe_size,
+                       uint64_t support, bool normalized, uint32_t top, uint64_t max_combinations,
+                       uint32_t* out_combo, uint64_t* out_count, double* out_value, uint32_t* n_out,
+                       uint64_t stats[3]) {
+  DAS_CHECK(k == 2 || k == 3, DAS_E_INVALID, "mine: k outside 2..3");
+  miner_check(c);
+  DAS_CHECK((tpl || !m) && (tpl_count || !m) && (basics || !nb) && (cands || !nc) && out_combo && out_count &&
+                out_value && n_out && stats,
+            DAS_E_INVALID, "mine: null argument");
+  DAS_CHECK(top >= 1 && top <= DAS_MX_MAX_TOP, DAS_E_INVALID, "mine: top outside 1..DAS_MX_MAX_TOP");
+  DAS_CHECK(universe_size > 0, DAS_E_INVALID, "mine: universe size 0");
+  DAS_CHECK(m < (1ull << 32), DAS_E_UNSUPPORTED, "mine: too many templates in one call");
+  cj_check_templates(c.idx, tpl, m);
+  std::vector<uint8_t> seen(m, 0);                     // bit 0: a basic, bit 1: a candidate
+  for (uint64_t i = 0; i < nb; ++i) {
+    DAS_CHECK(basics[i] < m, DAS_E_INVALID, "mine: template index out of range");
+    DAS_CHECK(!(seen[basics[i]] & 1), DAS_E_INVALID, "mine: a basic twice");
+    seen[basics[i]] |= 1;
+  }
+  for (uint64_t i = 0; i < nc; ++i) {
+    DAS_CHECK(cands[i] < m, DAS_E_INVALID, "mine: template index out of range");
+    DAS_CHECK(!(seen[cands[i]] & 2), DAS_E_INVALID, "mine: a candidate twice");
+    seen[cands[i]] |= 2;
+  }
+  DAS_CHECK(nb * nc < (1ull << 32), DAS_E_UNSUPPORTED, "mine: basics x candidates of 2^32 pairs or more");
+  uint64_t searched = 0;                               // the space as defined: < nb nc^2 / 2 < 2^63
+  for (uint64_t i = 0; i < nb; ++i) {
+    const uint64_t av = nc - (seen[basics[i]] & 2 ? 1 : 0);
+    searched += k == 2 ? av : av >= 2 ? mx_pairs(av) : 0;
+  }
+  *n_out = 0;
+  stats[0] = searched;
+  stats[1] = stats[2] = 0;
+  const uint64_t n2 = nb * nc;
+  if (!n2) return;
+  stats[1] = n2;
+  DAS_CHECK(n2 <= max_combinations, DAS_E_LIMIT,
+            "mine: " + std::to_string(n2) + " combinations to score, more than max_combinations");
+
+  hipStream_t s = c.s;
+  const uint64_t tile = mx_tile();
+  DBuf<CjTerm> terms;
+  cj_resolve(c, tpl, m, terms);
+  DBuf<unsigned long long> tcount(m, s), pcount(n2, s);
+  DBuf<uint32_t> ids(nb + nc, s);
+  DAS_HIP(hipMemcpyAsync(tcount.p, tpl_count, 8 * m, hipMemcpyHostToDevice, s));
+  DAS_HIP(hipMemcpyAsync(ids.p, basics, 4 * nb, hipMemcpyHostToDevice, s));
+  DAS_HIP(hipMemcpyAsync(ids.p + nb, cands, 4 * nc, hipMemcpyHostToDevice, s));
+  const uint32_t *d_basics = ids.p, *d_cands = ids.p + nb;
+
+  // the pair matrix, a tile of rows at a time
+  DBuf<uint32_t> combo(3 * std::min(tile, n2), s);
+  for (uint64_t r0 = 0; r0 < n2; r0 += tile) {
+    const uint64_t n = std::min(tile, n2 - r0);
+    {
+      ProfScope ps(c, "k_mx_pair_rows", 16.0 * n);
+      hipLaunchKernelGGL(k_mx_pair_rows, G(n), dim3(kB), 0, s, r0, n, nc, d_basics, d_cands, combo.p);
+      DAS_HIP(hipGetLastError());
+    }
+    cj_count_rows(c, terms.p, combo.p, n, 2, pcount.p + r0);
+  }
+
+  // the partner lists and the ranks of the triples
+  DBuf<uint32_t> part_tpl;
+  DBuf<unsigned long long> part_cnt;
+  DBuf<uint64_t> offs;                                 // s_off[nb + 1], pre[nb + 1]
+  std::vector<uint64_t> h_pre(nb + 1, 0);              // (uploaded below: lives to the end of the call)
+  uint64_t total = n2;                                 // ranks to score: k = 2, the matrix rows
+  if (k == 3) {
+    const MxPartnerIn in{pcount.p, d_basics, d_cands, nc};
+    DBuf<uint32_t> pos(n2, s);
+    exclusive_scan_fn<uint32_t>(in, n2, pos.p, s);
+    part_tpl.alloc(n2, s);
+    part_cnt.alloc(n2, s);
+    offs.alloc(2 * (nb + 1), s);
+    {
+      ProfScope ps(c, "k_mx_partners", n2 * (8.0 + 4.0 + 4.0 + 12.0) + 8.0 * (nb + 1));
+      hipLaunchKernelGGL(k_mx_partners, G(n2), dim3(kB), 0, s, n2, nb, in, (const uint32_t*)pos.p, part_tpl.p,
+                         part_cnt.p, offs.p);
+      DAS_HIP(hipGetLastError());
+    }
+    std::vector<uint64_t> h_off(nb + 1);
+    DAS_HIP(hipMemcpyAsync(h_off.data(), offs.p, 8 * (nb + 1), hipMemcpyDeviceToHost, s));
+    DAS_HIP(hipStreamSynchronize(s));
+    count_readback();
+    for (uint64_t b = 0; b < nb; ++b) {
+      DAS_CHECK(h_off[b] <= h_off[b + 1] && h_off[b + 1] - h_off[b] <= nc, DAS_E_INTERNAL,
+                "mine: partner list out of range");
+      h_pre[b + 1] = h_pre[b] + mx_pairs(h_off[b + 1] - h_off[b]);      // the lists are disjoint parts of n2 < 2^32
+    }
+    total = h_pre[nb];
+    stats[1] = n2 + total;
+    DAS_CHECK(stats[1] <= max_combinations, DAS_E_LIMIT,
+              "mine: " + std::to_string(stats[1]) + " combinations to score, more than max_combinations");
+    DAS_HIP(hipMemcpyAsync(offs.p + nb + 1, h_pre.data(), 8 * (nb + 1), hipMemcpyHostToDevice, s));
+  }
+
+  // tiles of ranks: count, score, keep the best `top`
+  const uint64_t tn = std::min(tile, std::max<uint64_t>(total, 1));
+  DBuf<uint32_t> combo2, aux, flag(tn, s), pos(tn + 1, s), keys, perm;
+  DBuf<unsigned long long> cnt3, cnt2;
+  DBuf<double> value(tn, s);
+  if (k == 3) {
+    if (combo.n < 3 * tn) combo.alloc(3 * tn, s);
+    combo2.alloc(2 * tn, s);
+    aux.alloc(2 * tn, s);
+    cnt3.alloc(tn, s);
+    cnt2.alloc(tn, s);
+  }
+  MxSel sel[2];
+  sel[0].alloc(top + tn, k, s);
+  sel[1].alloc(top + tn, k, s);
+  keys.alloc(2 * (top + tn), s);
+  perm.alloc(top + tn, s);
+  const double u = (double)universe_size;
+  uint64_t kept = 0, tiles = 0;
+  int cur = 0;
+  for (uint64_t g0 = 0; g0 < total; g0 += tile, ++tiles) {
+    const uint64_t n = std::min(tile, total - g0);
+    const unsigned long long* cnt = nullptr;
+    if (k == 2) {
+      ProfScope ps(c, "k_mx_pair_rows", 16.0 * n);
+      hipLaunchKernelGGL(k_mx_pair_rows, G(n), dim3(kB), 0, s, g0, n, nc, d_basics, d_cands, combo.p);
+      DAS_HIP(hipGetLastError());
+      cnt = pcount.p + g0;
+    } else {
+      {
+        // per rank: ~log2(nb) prefix words, two offsets, two partner ids; the rows written
+        ProfScope ps(c, "k_mx_enum", n * (8.0 * 4.0 + 16.0 + 8.0 + 12.0 + 8.0 + 8.0));
+        hipLaunchKernelGGL(k_mx_enum, G(n), dim3(kB), 0, s, g0, n, (uint32_t)nb, (const uint64_t*)(offs.p + nb + 1),
+                           (const uint64_t*)offs.p, d_basics, (const uint32_t*)part_tpl.p, combo.p, combo2.p, aux.p);
+        DAS_HIP(hipGetLastError());
+      }
+      cj_count_rows(c, terms.p, combo.p, n, 3, cnt3.p);
+      cj_count_rows(c, terms.p, combo2.p, n, 2, cnt2.p);
+      cnt = cnt3.p;
+    }
+    {
+      // per row: its indices, the terms' counts, its own and the pair counts; value and flag
+      ProfScope ps(c, "k_mx_score", n * (4.0 * k + 8.0 * k + 8.0 + (k == 3 ? 8.0 + 24.0 : 0.0) + 12.0));
+      hipLaunchKernelGGL(k_mx_score, G(n), dim3(kB), 0, s, n, k, (const uint32_t*)combo.p,
+                         (const unsigned long long*)tcount.p, cnt, (const unsigned long long*)cnt2.p,
+                         (const uint32_t*)aux.p, (const unsigned long long*)part_cnt.p, u,
+                         (unsigned long long)support, normalized ? 1u : 0u, value.p, flag.p);
+      DAS_HIP(hipGetLastError());
+    }
+    const uint64_t ns = scan_total<uint32_t>(SpanIn<uint32_t>{flag.p}, n, pos.p, s);   // the tile's read-back
+    DAS_CHECK(ns <= n, DAS_E_INTERNAL, "mine: more survivors than rows");
+    if (!ns) continue;
+    MxSel &A = sel[cur], &B = sel[cur ^ 1];
+    {
+      ProfScope ps(c, "k_mx_emit", 8.0 * n + ns * (4.0 * k + 16.0) * 2.0);
+      hipLaunchKernelGGL(k_mx_emit, G(n), dim3(kB), 0, s, n, k, (const uint32_t*)flag.p, (const uint32_t*)pos.p,
+                         (const uint32_t*)combo.p, cnt, (const double*)value.p, kept, A.combo.p, A.cnt.p, A.val.p);
+      DAS_HIP(hipGetLastError());
+    }
+    const uint64_t have = kept + ns, take = std::min<uint64_t>(have, top);
+    {
+      ProfScope ps(c, "k_mx_keys", 16.0 * have);
+      hipLaunchKernelGGL(k_mx_keys, G(have), dim3(kB), 0, s, have, (const double*)A.val.p, keys.p, keys.p + have);
+      DAS_HIP(hipGetLastError());
+    }
+    ColSet cs{};
+    cs.n = 2;
+    cs.c[0] = keys.p;
+    cs.c[1] = keys.p + have;
+    sort_perm(cs, have, perm.p, 32, s);
+    {
+      ProfScope ps(c, "k_mx_take", take * (4.0 + (4.0 * k + 16.0) * 2.0));
+      hipLaunchKernelGGL(k_mx_take, G(take), dim3(kB), 0, s, take, k, (const uint32_t*)perm.p,
+                         (const uint32_t*)A.combo.p, (const unsigned long long*)A.cnt.p, (const double*)A.val.p,
+                         B.combo.p, B.cnt.p, B.val.p);
+      DAS_HIP(hipGetLastError());
+    }
+    kept = take;
+    cur ^= 1;
+  }
+  stats[2] = tiles;
+  *n_out = (uint32_t)kept;
+  if (kept) {
+    const MxSel& A = sel[cur];
+    DAS_HIP(hipMemcpyAsync(out_combo, A.combo.p, 4 * kept * k, hipMemcpyDeviceToHost, s));
+    DAS_HIP(hipMemcpyAsync(out_count, A.cnt.p, 8 * kept, hipMemcpyDeviceToHost, s));
+    DAS_HIP(hipMemcpyAsync(out_value, A.val.p, 8 * kept, hipMemcpyDeviceToHost, s));
+  }
+  DAS_HIP(hipStreamSynchronize(s));                    // also before the buffers above go back to the allocator
   count_readback();
 }
 

@@ -25,6 +25,7 @@ enum Status : int {
   DAS_E_INTERNAL = -5,
   DAS_E_ATTRIBUTE = -6,   // the reference raises AttributeError here -> AttributeError
   DAS_E_SYNTAX = -7,      // malformed input where the reference asserts -> AssertionError
+  DAS_E_LIMIT = -8,       // more work than the caller's limit allows   -> ValueError
 };
 
 #define DAS_CHECK(cond, code, msg)                 \

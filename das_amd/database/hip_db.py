@@ -179,6 +179,7 @@ class HipDB(RelationalDB):
         self.name_search_stats = {"device": 0, "host": 0}   # get_matched_node_name calls answered by each path
         self.miner_stats = {"device": 0, "host": 0}         # halo / pattern_counts calls answered by each path
         self.conjunction_stats = {"device": 0, "host": 0}   # conjunction_counts: combinations counted by each path
+        self.mine_stats = {"device": 0, "host": 0}          # mine: calls answered by each path
 
     def __repr__(self):
         return "<HipDB>"
@@ -783,6 +784,45 @@ class HipDB(RelationalDB):
     def isurprisingness(self, pc, combos, universe_size, normalized=False):
         """miner.isurprisingness over this DB."""
         return _miner.isurprisingness(self, pc, combos, universe_size, normalized)
+
+    def mine(self, pc, basics, universe_size, ngram=3, support=0, normalized=False, top=16, candidates=None,
+             max_combinations=2**32):
+        """The notebook's exhaustive cell (efac9ac6) as one call (miner.mine):
+        for every basic (row indices into `pc`, the notebook's
+        pattern_handles[0]) every ascending (ngram - 1)-tuple of candidates
+        (default: every row of `pc`), counted, scored with
+        compute_isurprisingness and cut to the best `top`: a
+        miner.MiningResult.  One das_mine_combinations call: only the
+        templates the basics and candidates use go up, the combinations are
+        enumerated, counted, scored and selected on the device, for ngram 3
+        only inside each basic's partner lists (`.scored` < `.searched`).
+        miner.mine_host, the per-batch loop, answers with DAS_MINER=0,
+        CONFIG['no_overload'], stale pattern entries, a shard of several, a
+        `pc` without this DB's atom ids and when a basic or candidate is a
+        Similarity / Set template.  ValueError, the number in the message, if
+        the path would score more than max_combinations.  `mine_stats` counts
+        the calls of each path."""
+        from ..pattern_matcher.pattern_matcher import CONFIG
+        basics, cand = _miner.check_mine_args(pc, basics, universe_size, ngram, support, top, candidates)
+        device = (self._miner_on_device() and not CONFIG['no_overload'] and pc.db is self and pc.type_id is not None
+                  and isinstance(universe_size, (int, np.integer)) and universe_size < 2 ** 64)
+        used = np.union1d(basics, cand)
+        if device and len(used):
+            unordered = [self.type_id[t] for t in UNORDERED_LINK_TYPES if t in self.type_id]
+            device = not np.isin(pc.type_id[used], unordered).any()
+        if not device:
+            self.mine_stats["host"] += 1
+            return _miner.mine_host(self, pc, basics, universe_size, ngram, support, normalized, top, cand,
+                                    max_combinations)
+        tpl = np.vstack([pc.arity[used], pc.type_id[used], pc.targets[used].T]) if len(used) else \
+            np.zeros((5, 0), dtype=np.uint32)
+        combos, count, value, (_, scored, tiles) = self.ctx.mine_combinations(
+            tpl, np.asarray(pc.count)[used], np.searchsorted(used, basics), np.searchsorted(used, cand), ngram,
+            int(universe_size), min(int(support), 2 ** 64 - 1), normalized, int(top),
+            min(int(max_combinations), 2 ** 64 - 1))
+        self.mine_stats["device"] += 1
+        return _miner.MiningResult(pc, used[combos.astype(np.int64)].astype(np.uint32).reshape(-1, ngram), count,
+                                   value, _miner.search_space_size(basics, cand, ngram), scored, tiles)
 
     def get_matched_node_name(self, node_type: str, substring: str) -> str:
         """redis_mongo_db.py:287-293 (Mongo $regex on names of that type).

@@ -258,6 +258,21 @@ class DistributedAtomSpace:
         from . import miner
         return miner.isurprisingness(self, pc, combos, universe_size, normalized)
 
+    def mine(self, pc, basics, universe_size, ngram=3, support=0, normalized=False, top=16, candidates=None,
+             max_combinations=2 ** 32):
+        """The notebook's exhaustive cell (efac9ac6) as one call: for every
+        basic (rows of `pc`, the notebook's pattern_handles[0]) every
+        ascending (ngram - 1)-tuple of candidate rows, counted, scored and
+        cut to the best `top`: a miner.MiningResult (`.combos`, `.count`,
+        `.value`, `.searched`, `.scored`, `.pattern(i)`).  On a HipDB one
+        device call; any other DBInterface runs miner.mine_host."""
+        from . import miner
+        if hasattr(self.db, "mine"):
+            return self.db.mine(pc, basics, universe_size, ngram=ngram, support=support, normalized=normalized,
+                                top=top, candidates=candidates, max_combinations=max_combinations)
+        return miner.mine_host(self, pc, basics, universe_size, ngram, support, normalized, top, candidates,
+                               max_combinations)
+
     def query(self, query: LogicalExpression, output_format: QueryOutputFormat = QueryOutputFormat.HANDLE) -> str:
         """distributed_atom_space.py:298-321"""
         query_answer = PatternMatchingAnswer()

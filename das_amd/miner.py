@@ -21,6 +21,11 @@ The mining loop (cells c34c1d24 / efac9ac6) is the third step:
 templates, `HipDB.conjunction_counts` counts a batch of them from the index
 (das_conjunction_counts) and `isurprisingness` adds the notebook's score, the
 sub-combinations it needs counted once per batch.
+
+`mine` is the exhaustive cell (efac9ac6) as one call: every basic with every
+ascending tuple of candidates, counted, scored and cut to the best rows.
+`mine_host` is its definition over `isurprisingness`; `HipDB.mine` enumerates,
+counts, scores and selects on the device (das_mine_combinations).
 """
 import itertools
 import time
@@ -514,3 +519,141 @@ def isurprisingness(db, pc, combos, universe_size, normalized=False):
         sub[3] = flat_triple_counts(terms, sub[2], sub[3])
     value = isurprisingness_from_counts(count, terms, universe_size, sub.get(2), sub.get(3), normalized)
     return ISurprisingness(count, value)
+
+
+# ---------------------------------------------------------------------------
+# the exhaustive cell (efac9ac6) as one call
+# ---------------------------------------------------------------------------
+
+MINE_MAX_TOP = _lib.MX_MAX_TOP
+
+
+class MiningResult:
+    """The best rows of a `mine` call, by value descending (ties in
+    enumeration order): `.combos` (r, ngram) uint32 row indices into `.pc`,
+    the basic first; `.count` uint64; `.value` float64; `.searched`, the rows
+    of the search space; `.scored`, the combinations the path counted;
+    `.tiles` (device path); `.pattern(i)`, the composite pattern of row i,
+    ready for das.query.  `.stopped`: mine_host with a time budget that ran
+    out (measurement tools only)."""
+
+    def __init__(self, pc, combos, count, value, searched, scored, tiles=0):
+        self.pc = pc
+        self.combos = combos
+        self.count = count
+        self.value = value
+        self.searched = int(searched)
+        self.scored = int(scored)
+        self.tiles = int(tiles)
+        self.stopped = None
+
+    def __len__(self):
+        return len(self.count)
+
+    def pattern(self, i):
+        return build_composite_pattern([self.pc.pattern(int(j)) for j in self.combos[i]])
+
+
+def _index_list(values, m, what):
+    a = np.asarray(values if isinstance(values, np.ndarray) else list(values))
+    if a.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    if a.ndim != 1 or a.dtype.kind not in "iu":
+        raise ValueError(f"mine: {what} are a list of template indices")
+    a = a.astype(np.int64)
+    if a.min() < 0 or a.max() >= m:
+        raise ValueError(f"mine: a template index of the {what} is out of range")
+    if len(np.unique(a)) != len(a):
+        raise ValueError(f"mine: the {what} are distinct")
+    return a
+
+
+def check_mine_args(pc, basics, universe_size, ngram, support, top, candidates):
+    """(basics in the order given, candidates ascending) as int64 arrays.
+    ValueError: ngram outside {2, 3}, an index out of range or twice, top
+    outside 1..MINE_MAX_TOP, a universe size or support that is not a count."""
+    if ngram not in (2, 3):
+        raise ValueError("mine: ngram outside {2, 3}")
+    basics = _index_list(basics, len(pc), "basics")
+    candidates = np.arange(len(pc), dtype=np.int64) if candidates is None else \
+        np.sort(_index_list(candidates, len(pc), "candidates"))
+    if not isinstance(top, (int, np.integer)) or not 1 <= top <= MINE_MAX_TOP:
+        raise ValueError(f"mine: top outside 1..{MINE_MAX_TOP}")
+    if not universe_size > 0:
+        raise ValueError("mine: universe size 0")
+    if support < 0:
+        raise ValueError("mine: negative support")
+    return basics, candidates
+
+
+def search_space_size(basics, candidates, ngram):
+    """Rows of the search space: per basic the (ngram - 1)-subsets of the
+    candidates other than itself."""
+    total = 0
+    for own in np.isin(basics, candidates).tolist():
+        av = len(candidates) - int(own)
+        total += av if ngram == 2 else av * (av - 1) // 2
+    return total
+
+
+def _keep_best(kept, new, top):
+    """kept + new (tuples of combos, count, value; kept's rows enumerated
+    first), stable by value descending, cut to top."""
+    combos, count, value = (np.concatenate([a, b]) for a, b in zip(kept, new))
+    order = np.argsort(-value, kind="stable")[:top]
+    return combos[order], count[order], value[order]
+
+
+def mine_host(db, pc, basics, universe_size, ngram=3, support=0, normalized=False, top=16, candidates=None,
+              max_combinations=2**32, batch=1 << 15, budget_s=None):
+    """The definition of `mine`: for each basic, in the order given, every
+    strictly ascending (ngram - 1)-tuple of candidates that does not hold it,
+    as the row (b, c1[, c2]); count and value of each row from
+    `isurprisingness`, `batch` rows at a time; the rows with count >= support
+    and value > 0 by value descending, ties in enumeration order, cut to
+    `top`.  ValueError if the space has more than max_combinations rows.
+    budget_s: stop after that many seconds (`.stopped` = {done, of})."""
+    basics, candidates = check_mine_args(pc, basics, universe_size, ngram, support, top, candidates)
+    searched = search_space_size(basics, candidates, ngram)
+    if searched > max_combinations:
+        raise ValueError(f"mine: {searched} combinations to score, more than max_combinations")
+    kept = (np.zeros((0, ngram), dtype=np.uint32), np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.float64))
+    t0 = time.perf_counter()
+    done, stopped = 0, None
+
+    def rows_of():
+        for b in basics.tolist():
+            for tup in itertools.combinations([c for c in candidates.tolist() if c != b], ngram - 1):
+                yield (b, *tup)
+
+    rows = rows_of()
+    while stopped is None:
+        chunk = np.array(list(itertools.islice(rows, batch)), dtype=np.uint32).reshape(-1, ngram)
+        if not len(chunk):
+            break
+        if budget_s is not None and time.perf_counter() - t0 > budget_s:
+            stopped = {"done": done, "of": searched}
+            break
+        res = isurprisingness(db, pc, chunk, universe_size, normalized)
+        with np.errstate(invalid="ignore"):
+            ok = (res.value > 0) & (res.count >= support)
+        if ok.any():
+            kept = _keep_best(kept, (chunk[ok], np.asarray(res.count)[ok], np.asarray(res.value)[ok]), top)
+        done += len(chunk)
+    out = MiningResult(pc, *kept, searched, done)
+    out.stopped = stopped
+    return out
+
+
+def mine(db, pc, basics, universe_size, ngram=3, support=0, normalized=False, top=16, candidates=None,
+         max_combinations=2**32):
+    """The notebook's exhaustive cell as one call: the best `top` patterns
+    And(b, c1[, c2]) over every basic b and every ascending tuple of
+    candidates (default: every template of `pc`), a MiningResult; with top=1
+    its row is the notebook's best_pattern.  A HipDB enumerates, counts,
+    scores and selects on the device (`HipDB.mine`); any other DB runs
+    `mine_host`."""
+    if hasattr(db, "mine"):
+        return db.mine(pc, basics, universe_size, ngram=ngram, support=support, normalized=normalized, top=top,
+                       candidates=candidates, max_combinations=max_combinations)
+    return mine_host(db, pc, basics, universe_size, ngram, support, normalized, top, candidates, max_combinations)

@@ -39,6 +39,7 @@ typedef struct das_table das_table_t;
 #define DAS_ERR_INTERNAL (-5)
 #define DAS_ERR_ATTRIBUTE (-6)  /* where the reference raises AttributeError (:359-360) */
 #define DAS_ERR_SYNTAX (-7)     /* malformed input where the reference asserts (canonical_parser.py:307-310) */
+#define DAS_ERR_LIMIT (-8)      /* more work than the caller's limit allows (das_mine_combinations) */
 
 #define DAS_NONE 0xFFFFFFFFu   /* "no atom / wildcard" id */
 
@@ -297,6 +298,39 @@ int das_pattern_counts(das_ctx_t* ctx, const das_table_t* links, const uint32_t*
  * each before anything is launched.  n == 0: DAS_OK, nothing launched. */
 int das_conjunction_counts(das_ctx_t* ctx, const uint32_t* tpl, uint64_t m, const uint32_t* combo, uint64_t n,
                            uint32_t k, uint64_t* counts);
+#define DAS_MX_TILE (1u << 20)      /* combinations of one tile of the exhaustive search (env DAS_MX_TILE overrides) */
+#define DAS_MX_MAX_TOP 65536        /* rows das_mine_combinations returns at most */
+/* The notebook's exhaustive cell (efac9ac6) for ngram k = 2 or 3: for every
+ * basic b, in the order given, every (k - 1)-tuple of candidates at ascending
+ * positions of `candidates` that does not hold b -- the row (b, c1[, c2]) -- is
+ * counted as das_conjunction_counts counts it and scored with
+ * compute_isurprisingness in float64 (IEEE division and multiplication in the
+ * notebook's order: (t0 t1) t2, p01 t2, p02 t1, p12 t0; normalized divides by
+ * count / universe_size and gives nan where the count is 0).  Reported: the
+ * rows with count >= support and value > 0, by value descending, ties in
+ * enumeration order, the first `top` of them: out_combo[top * k] (indices into
+ * tpl), out_count[top], out_value[top], *n_out rows filled.  `tpl` as for
+ * das_conjunction_counts, `tpl_count[m]` the templates' own counts, `basics`
+ * and `candidates` distinct indices into tpl (a basic may be a candidate).
+ * k = 3 counts count(b, c) of all basics x candidates first and enumerates only
+ * the pairs i < j of each basic's partners (count(b, c) > 0): any other triple
+ * has a pair count of 0 and so the value 0 (nan if normalized).  k = 2 scores
+ * that matrix.  Nothing but the templates goes up; one read-back of the partner
+ * list sizes, one per tile of DAS_MX_TILE combinations (its survivor count),
+ * one of the result.  stats[0] = the rows of the search space as defined above
+ * (below 2^63), stats[1] = the combinations counted (the matrix, plus the
+ * enumerated triples), stats[2] = tiles scored.  stats[1] > max_combinations:
+ * DAS_ERR_LIMIT with stats[0..1] filled, before any tile is scored.  k outside
+ * 2..3, an index >= m, a basic or a candidate twice, top == 0 or >
+ * DAS_MX_MAX_TOP, universe_size == 0, a null pointer, a bad template:
+ * DAS_ERR_INVALID; a Similarity / Set template, basics x candidates of 2^32
+ * pairs or more: DAS_ERR_UNSUPPORTED; no index: DAS_ERR_NOT_BUILT; a sharded
+ * index with world > 1: DAS_ERR_UNSUPPORTED -- each before anything is launched. */
+int das_mine_combinations(das_ctx_t* ctx, const uint32_t* tpl, uint64_t m, const uint64_t* tpl_count,
+                          const uint32_t* basics, uint64_t n_basics, const uint32_t* candidates, uint64_t n_candidates,
+                          uint32_t k, uint64_t universe_size, uint64_t support, uint32_t normalized, uint32_t top,
+                          uint64_t max_combinations, uint32_t* out_combo, uint64_t* out_count, double* out_value,
+                          uint32_t* n_out, uint64_t stats[3]);
 
 /* ---- query operators ----------------------------------------------------- */
 /* One Link with >= 1 wildcard, evaluated against the pattern index

@@ -24,7 +24,17 @@ one for their merged pairs); the host path is the per-query loop
 the same budget.  The device child also counts a batch of 10^5 random pairs.
 The record states launches and read-backs per call.
 
---steps names the steps to measure (default: all three).  With fewer, the
+Fourth step, "exhaustive": the notebook's last cell (efac9ac6) for NGRAM 3
+over the same templates -- every level-0 template with every pair of templates
+-- as one db.mine call (das_mine_combinations: the pair matrix, the partner
+lists, tiles of enumerated triples counted, scored and cut to the best 16).
+The baseline is the only way there was before: the host enumerates the same
+(unpruned) space and scores it in batches through miner.isurprisingness on
+the same HipDB (miner.mine_host; the counting itself is das_conjunction_counts),
+under --host-budget; if it does not finish it is extrapolated per row from
+the part done, and the record says so.  Both run in the device child.
+
+--steps names the steps to measure (default: all four).  With fewer, the
 halo host loop is not run unless asked for, and the steps measured replace
 those of the record already at --out, whose other steps stay as they are;
 "steps_measured_last" then says which ones the last run wrote.
@@ -49,9 +59,11 @@ HBM_PEAK_SPEC = 8.0e12          # bytes/s, MI355X HBM3E (spec)
 LENGTH = 2
 MINER_KERNELS = ("k_halo_seed_bits", "k_halo_mark_links", "k_halo_mark_targets", "k_bits_count", "k_bits_emit",
                  "k_pc_templates", "k_pc_flags", "k_pc_emit", "k_pc_resolve", "k_pc_scan", "k_pc_finish",
-                 "k_cj_resolve", "k_cj_plan", "k_cj_count")
+                 "k_cj_resolve", "k_cj_plan", "k_cj_count", "k_mx_pair_rows", "k_mx_partners", "k_mx_enum",
+                 "k_mx_score", "k_mx_emit", "k_mx_keys", "k_mx_take")
+MX_TOP, MX_BATCH = 16, 1 << 17
 NGRAM, EPOCHS, PAIR_BATCH, MINING_SEED = 3, 1000, 100_000, 20240229
-STEPS = ("halo", "counts", "mining")
+STEPS = ("halo", "counts", "mining", "exhaustive")
 
 
 def halo_queries(atoms_expanded, links_found):
@@ -85,6 +97,47 @@ def level_rows(np, db, pc, links_per_level):
                              *(q.targets[:, p].tolist() for p in range(3))))
     at = {k: i for i, k in enumerate(key(pc))}
     return [np.asarray([at[k] for k in key(db.pattern_counts(links))], dtype=np.int64) for links in links_per_level]
+
+
+def exhaustive_step(args, np, _lib, miner, db, pc, basics, universe, log):
+    """db.mine over (basics x pairs of all templates) and its baseline, the
+    host enumeration scored through miner.isurprisingness on the same HipDB."""
+    db.mine(pc, basics[:1], universe, ngram=2, top=1)                              # first call: allocations
+    db.ctx.sync()
+    c0 = _lib.counters()
+    t0 = time.perf_counter()
+    res = db.mine(pc, basics, universe, ngram=NGRAM, top=MX_TOP, max_combinations=2 ** 62)
+    t_dev = time.perf_counter() - t0
+    c1 = _lib.counters()
+    assert db.mine_stats["host"] == 0
+    dev = {"ngram": NGRAM, "templates": len(pc), "basics": len(basics), "top": MX_TOP,
+           "searched": res.searched, "scored": res.scored, "tiles": res.tiles, "seconds": round(t_dev, 6),
+           "us_per_combination_scored": round(1e6 * t_dev / max(res.scored, 1), 5),
+           "us_per_combination_searched": round(1e6 * t_dev / max(res.searched, 1), 7),
+           "launches": c1[0] - c0[0], "readbacks": c1[1] - c0[1], "rows": len(res),
+           "best": {"combo": res.combos[0].tolist(), "count": int(res.count[0]), "value": float(res.value[0])}
+           if len(res) else None}
+    log(f"exhaustive {dev}")
+    t0 = time.perf_counter()
+    base = miner.mine_host(db, pc, basics, universe, ngram=NGRAM, top=MX_TOP, max_combinations=2 ** 62,
+                           batch=MX_BATCH, budget_s=args.host_budget)
+    t_base = time.perf_counter() - t0
+    rec = {"how": "miner.mine_host: itertools enumeration of the whole space, miner.isurprisingness "
+                  f"(das_conjunction_counts) per batch of {MX_BATCH} rows, on the same HipDB",
+           "searched": base.searched, "budget_s": args.host_budget, "seconds_measured": round(t_base, 3),
+           "stopped": base.stopped}
+    if base.stopped is None:
+        assert base.combos.tolist() == res.combos.tolist() and base.value.tolist() == res.value.tolist()
+        total = t_base
+    else:
+        done = max(base.stopped["done"], 1)
+        total = t_base * base.stopped["of"] / done
+        rec["extrapolated"] = f"{base.stopped['done']} of {base.stopped['of']} rows scored; " \
+                              "seconds = measured * of / done"
+        rec["us_per_combination_measured"] = round(1e6 * t_base / done, 4)
+    rec["seconds"] = round(total, 3)
+    log(f"exhaustive baseline {rec}")
+    return {"exhaustive": dev, "exhaustive_baseline": rec}
 
 
 def child(args):
@@ -168,7 +221,9 @@ def child(args):
                              "nonzero": int((pair_counts > 0).sum()), "count_sum": int(pair_counts.sum())}
         out["mining_combos"] = combos.tolist()
         out["mining_digest"] = [int(res.count.sum()), int((res.count > 0).sum())]
-        # per-kernel times (events) of one more run of both steps
+        if "exhaustive" in args.steps:
+            out.update(exhaustive_step(args, np, _lib, miner, db, pc, rows[0].tolist(), universe, log))
+        # per-kernel times (events) of one more run of the steps
         db.ctx.prof_enable(True)
         db.ctx.prof_reset()
         h2 = db.halo(seed, LENGTH)
@@ -184,6 +239,15 @@ def child(args):
                 ks[name] = {"launches": int(st["launches"]), "ms": round(ms, 4), "bytes": st["bytes"],
                             "hbm_fraction_of_spec": round(st["bytes"] / (ms * 1e-3) / HBM_PEAK_SPEC, 4) if ms else None}
         out["kernels"] = ks
+        if "exhaustive" in args.steps:
+            # one more db.mine under the events, its kernels apart: it shares the counting kernels with the mining step
+            db.ctx.prof_reset()
+            db.mine(pc, rows[0].tolist(), universe, ngram=NGRAM, top=MX_TOP, max_combinations=2 ** 62)
+            db.ctx.sync()
+            mx = {name: {"launches": int(st["launches"]), "ms": round(st["ms"], 4), "bytes": st["bytes"]}
+                  for name, st in db.ctx.prof_stats().items() if st["launches"]}
+            out["exhaustive"]["kernels"] = mx
+            out["exhaustive"]["kernel_ms"] = round(sum(r["ms"] for r in mx.values()), 4)
         db.ctx.prof_enable(False)
     else:
         os.environ["DAS_MINER"] = "0"
@@ -285,11 +349,15 @@ def main():
     expect = {"links_per_level": dev["halo"]["links_per_level"], "atoms_expanded": dev["halo"]["atoms_expanded"],
               "sample_ids": dev.pop("sample_ids"), "counts_digest": dev.pop("counts_digest"),
               "mining_combos": dev.pop("mining_combos"), "mining_digest": dev.pop("mining_digest")}
-    r = subprocess.run(base + ["--mode", "host", "--expect", json.dumps(expect)], env=dict(env, DAS_MINER="0"),
-                       stdout=subprocess.PIPE, text=True, check=True)
-    host = json.loads(r.stdout.strip().splitlines()[-1])
+    host_steps = [x for x in args.steps if x != "exhaustive"]          # (its baseline ran in the device child)
+    host = {}
+    if host_steps:
+        r = subprocess.run(base + ["--mode", "host", "--expect", json.dumps(expect)], env=dict(env, DAS_MINER="0"),
+                           stdout=subprocess.PIPE, text=True, check=True)
+        host = json.loads(r.stdout.strip().splitlines()[-1])
+        assert host["conjunction_path"]["device"] == 0
     assert dev["path"]["host"] == 0 and dev["path"]["device"] > 0
-    assert dev["mining"]["on_device"] > 0 and host["conjunction_path"]["device"] == 0
+    assert dev["mining"]["on_device"] > 0
     if set(args.steps) != set(STEPS) and os.path.exists(args.out):
         # only the steps asked for are taken from this run; the record's other steps stay
         with open(args.out) as f:
@@ -297,8 +365,9 @@ def main():
         same_kb = all(old.get(k) == rec[k] for k in ("kb", "genes", "schemas", "rows_per_schema", "halo_length", "seed"))
         assert same_kb, "the record at --out is of another KB: measure all steps"
         keep = {"halo": ("halo",), "counts": ("counts", "counts_whole_level_1"),
-                "mining": ("mining", "pair_batch", "conjunction_path")}
-        names = {"halo": ("k_halo", "k_bits"), "counts": ("k_pc_",), "mining": ("k_cj_",)}
+                "mining": ("mining", "pair_batch", "conjunction_path"),
+                "exhaustive": ("exhaustive", "exhaustive_baseline")}
+        names = {"halo": ("k_halo", "k_bits"), "counts": ("k_pc_",), "mining": ("k_cj_",), "exhaustive": ("k_mx_",)}
         for side, new in (("device", dev), ("host", host)):
             for step in args.steps:
                 for k in keep[step]:
@@ -310,7 +379,11 @@ def main():
         dev, host, rec = old["device"], old["host"], old
     rec["steps_measured_last"] = args.steps
     rec["device"], rec["host"] = dev, host
-    for step in args.steps:
+    if "exhaustive" in args.steps:
+        d, h = dev["exhaustive"], dev["exhaustive_baseline"]
+        print(f"exhaustive: device {d['seconds']} s ({d['scored']} of {d['searched']} combinations scored, "
+              f"{d['tiles']} tiles), host enumeration {h['seconds']} s{', extrapolated' if 'extrapolated' in h else ''}")
+    for step in host_steps:
         d, h = dev[step], host[step]
         print(f"{step}: device {d['seconds']} s ({d['ms_per_query']} ms/query), host {h['seconds']} s "
               f"({h['ms_per_query']} ms/query{', extrapolated' if 'extrapolated' in h else ''})")
