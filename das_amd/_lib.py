@@ -78,6 +78,8 @@ class das_name_dfa_t(C.Structure):
 
 
 NAME_STAGE_BYTES = 16384          # DAS_NAME_STAGE_BYTES: name bytes of one tile the matcher stages in LDS
+NAME_COPY_WAVE = 64               # DAS_NAME_COPY_WAVE: a longer name is copied by a whole wave
+NAME_FETCH_GUESS = 32             # Context.node_names: bytes per name of the first call's capacity
 HALO_MAX_LEVELS = 8               # DAS_HALO_MAX_LEVELS
 HALO_BLOCK_ENTRIES = 1024         # DAS_HALO_BLOCK_ENTRIES: incoming-list entries one workgroup marks per pass
 PC_CHUNK_ROWS = 1024              # DAS_PC_CHUNK_ROWS: index rows one wave counts per step of a (1,2)-grounded template
@@ -128,6 +130,7 @@ _SIGS = {
     "das_incoming": (C.c_int, [P, C.c_uint32, P, C.c_uint64, P]),
     "das_match_node_names": (C.c_int, [P, C.c_uint32, P, P, C.c_uint64, P]),
     "das_node_name_stats": (C.c_int, [P, C.c_uint32, P, P, P]),
+    "das_node_names": (C.c_int, [P, P, C.c_uint64, P, C.c_int32, C.c_uint64, P, P, C.c_uint64, P, P, P]),
     "das_halo_expand": (C.c_int, [P, P, C.c_uint64, C.c_uint32, P, P]),
     "das_pattern_counts": (C.c_int, [P, P, P, C.c_uint64, C.POINTER(P)]),
     "das_conjunction_counts": (C.c_int, [P, P, C.c_uint64, P, C.c_uint64, C.c_uint32, P]),
@@ -329,6 +332,31 @@ def hex_to_digest(h):
         return np.frombuffer(bytes.fromhex(h), dtype="<u4").astype(np.uint32)
     except ValueError:
         raise ValueError(f"Invalid handle: {h}")
+
+
+def decode_names(off, data, kind):
+    """Context.node_names' (off, bytes, kind) as a list: the name of each
+    entry (UTF-8, as the loaders encoded it), None where kind is 0.  Every
+    entry's bytes must be there (off[n] <= len(bytes))."""
+    off = np.asarray(off, dtype=np.uint64)
+    kind = np.asarray(kind, dtype=np.uint8)
+    n = kind.size
+    if off.size != n + 1:
+        raise ValueError("decode_names: off must hold one more entry than kind")
+    o = off.tolist()
+    raw = bytes(memoryview(np.ascontiguousarray(data, dtype=np.uint8)))
+    if any(a > b for a, b in zip(o, o[1:])) or o[0] != 0 or o[-1] > len(raw):
+        raise ValueError("decode_names: offsets not ascending inside the bytes")
+    if raw.isascii():
+        # one code point per byte: one decode, then str slices
+        text = raw.decode("ascii")
+        out = [text[a:b] for a, b in zip(o, o[1:])]
+    else:
+        out = [raw[a:b].decode("utf-8") for a, b in zip(o, o[1:])]
+    if not kind.all():
+        for i in np.flatnonzero(kind == 0).tolist():
+            out[i] = None
+    return out
 
 
 class Table:
@@ -585,6 +613,55 @@ class Context:
         n = C.c_uint64()
         check(lib().das_match_node_names(self.h, int(type_id), C.byref(d), ptr(out), int(cap), C.byref(n)), self.h)
         return out[:min(n.value, int(cap))], n.value
+
+    def node_names(self, ids=None, table=None, col=0, row0=0, nrows=None, cap=None, out=None):
+        """(off, bytes, kind) of das_node_names: the names of `ids` (host
+        uint32 atom ids) or of rows [row0, row0 + nrows) (default: to the
+        end) of column `col` of a device Table, in input order.  off: uint64
+        [n + 1] byte offsets (off[n] = the true total), bytes: the UTF-8
+        names back to back, kind: uint8 [n], 1 = node, 0 = not a node (its
+        entry is empty); decode_names makes strings of them.  cap: copy at
+        most that many bytes (default: a guess, and a second call with the
+        total where it was short); out: a uint8 array of at least `cap`
+        bytes to copy into (`bytes` is then a view of it)."""
+        if (ids is None) == (table is None):
+            raise ValueError("node_names: give either ids or a table")
+        if table is not None:
+            col, row0 = int(col), int(row0)
+            if not 0 <= col < len(table.vars):
+                raise ValueError("node_names: bad column")
+            if row0 < 0 or row0 > table.nrows:
+                raise ValueError("node_names: rows out of range")
+            n = table.nrows - row0 if nrows is None else int(nrows)
+            if n < 0 or n > table.nrows - row0:
+                raise ValueError("node_names: rows out of range")
+            src, th = None, table.h
+        else:
+            ids = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32).ravel())
+            n, th, col, row0 = ids.size, None, 0, 0
+            src = ptr(ids) if n else None
+        if out is not None:
+            if out.dtype != np.uint8 or not out.flags.c_contiguous or out.ndim != 1:
+                raise ValueError("node_names: out must be a contiguous uint8 array")
+            if cap is None:
+                cap = out.size
+            elif int(cap) > out.size:
+                raise ValueError("node_names: cap exceeds the out buffer")
+        guess = cap is None
+        cap = NAME_FETCH_GUESS * n + 256 if guess else int(cap)
+        if cap < 0:
+            raise ValueError("node_names: negative cap")
+        off = np.zeros(n + 1, dtype=np.uint64)
+        kind = np.zeros(max(n, 1), dtype=np.uint8)
+        total, other = C.c_uint64(), C.c_uint64()
+        while True:
+            buf = out if out is not None else np.empty(max(cap, 1), dtype=np.uint8)
+            check(lib().das_node_names(self.h, src, n, th, col, row0, ptr(off), ptr(buf), cap, ptr(kind),
+                                       C.byref(total), C.byref(other)), self.h)
+            if not guess or total.value <= cap:
+                break
+            cap, guess = total.value, False
+        return off, buf[:min(total.value, cap)], kind[:n]
 
     def halo_expand(self, seed_ids, levels):
         """(links, atoms): per level one-column Tables of ascending ids, the

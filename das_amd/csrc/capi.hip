@@ -527,6 +527,21 @@ int das_node_name_stats(das_ctx_t* ctx, uint32_t type_id, uint64_t* n_nodes, uin
   });
 }
 
+int das_node_names(das_ctx_t* ctx, const uint32_t* ids, uint64_t n, const das_table_t* table, int32_t col,
+                   uint64_t row0, uint64_t* off, uint8_t* bytes, uint64_t cap, uint8_t* kind, uint64_t* n_bytes,
+                   uint64_t* n_other) {
+  return guarded(ctx, [&] {
+    DAS_CHECK(n_bytes, das::DAS_E_INVALID, "null argument");
+    const uint32_t* d_ids = nullptr;
+    if (table) {
+      DAS_CHECK(col >= 0 && col < table->t.ncols, das::DAS_E_INVALID, "bad column");
+      DAS_CHECK(row0 <= table->t.nrows && n <= table->t.nrows - row0, das::DAS_E_INVALID, "rows out of range");
+      d_ids = table->t.col(col) + row0;
+    }
+    *n_bytes = das::node_names(ctx->c, table ? nullptr : ids, d_ids, n, off, bytes, cap, kind, n_other);
+  });
+}
+
 int das_halo_expand(das_ctx_t* ctx, const uint32_t* seed_ids, uint64_t n_seeds, uint32_t levels,
                     das_table_t** links_out, das_table_t** atoms_out) {
   return guarded(ctx, [&] {

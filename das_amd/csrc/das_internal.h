@@ -377,6 +377,12 @@ void check_name_dfa(const das_name_dfa_t& d);
 // ids (ascending) of the nodes of `type_id` whose name `d` accepts: the
 // number of matches; min(that, cap) ids copied to the host array out_ids
 uint64_t match_node_names(Ctx& c, uint32_t type_id, const das_name_dfa_t& d, uint32_t* out_ids, uint64_t cap);
+// das_node_names: the names of the n ids at d_ids (device) or, d_ids null, at
+// h_ids (host), in input order; off[n + 1], kind[n] and min(total, cap) name
+// bytes copied to the host arrays; returns the total, *n_other = the entries
+// that are no node
+uint64_t node_names(Ctx& c, const uint32_t* h_ids, const uint32_t* d_ids, uint64_t n, uint64_t* off, uint8_t* bytes,
+                    uint64_t cap, uint8_t* kind, uint64_t* n_other);
 
 // miner.hip: SimplePatternMiner's bulk steps (das_halo_expand, das_pattern_counts)
 // links[l] / atoms[l], l < levels: the links first found at level l (arity 2

@@ -15,6 +15,9 @@
 // its name with one table lookup per byte and stops at the first accepting
 // state (accepting states are absorbing).  The kernel knows nothing about
 // regular expressions: das_name_dfa_t is the whole contract.
+//
+// Fetch (das_node_names): ids -> names, a gather over the same heap; its
+// kernels and their comment stand below the matcher's.
 #include <algorithm>
 #include <cstring>
 
@@ -299,7 +302,225 @@ void build_name_heap(Ctx& c) {
   h.built = true;
 }
 
+// ---------------------------------------------------------------------------
+// Name fetch (das_node_names): ids -> names, the heap read the other way.
+// Locate: one thread per input finds its id in the ascending node list (a
+// binary search: no id-indexed array is kept resident for it) and notes where
+// the name lies and how long it is.  A scan of the lengths gives the output
+// offsets.  Copy: a tile of kNameBlock consecutive entries is one contiguous
+// piece of the output; where it fits kFetchStage bytes the names are placed
+// in an LDS image of that piece and the image leaves in whole 16-byte stores,
+// else each name goes straight to the output.  Either way a name of up to
+// kCopyWave bytes is moved by its own lane and a longer one by its wave.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kCopyWave = DAS_NAME_COPY_WAVE;
+// the image: a tile's bytes from the 16-byte boundary at or below its first; a
+// tile of lane-copied names always fits
+constexpr uint32_t kFetchStage = kNameBlock * kCopyWave + 16;
+constexpr uint32_t kFetchVecs = kFetchStage / 16;
+static_assert(kFetchStage % 16 == 0 && kFetchStage <= 64 * 1024, "the image is whole vectors within LDS");
+constexpr uint32_t kMaxNameLen = 0xFFFFFFFFu;
+
+__global__ void k_name_locate(const uint32_t* __restrict__ ids, uint64_t n, const uint8_t* __restrict__ cat,
+                              uint64_t n_atoms, const uint32_t* __restrict__ node_id, uint64_t n_nodes,
+                              const uint64_t* __restrict__ hoff, uint64_t n_bytes, uint64_t* __restrict__ src,
+                              uint32_t* __restrict__ len, uint8_t* __restrict__ kind) {
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t id = ids[i];
+    uint64_t b = 0, l = 0;
+    uint8_t k = 0;
+    if (id < n_atoms && cat[id] == CAT_NODE) {
+      uint64_t lo = 0, hi = n_nodes;                            // the first slot whose id is >= id
+      while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (node_id[mid] < id) lo = mid + 1;
+        else hi = mid;
+      }
+      if (lo < n_nodes && node_id[lo] == id) {
+        k = 1;
+        const uint64_t o0 = hoff[lo], o1 = hoff[lo + 1];
+        if (o0 <= o1 && o1 <= n_bytes && o1 - o0 <= kMaxNameLen) {   // a name lies inside the heap
+          b = o0;
+          l = o1 - o0;
+        }
+      }
+    }
+    src[i] = b;
+    len[i] = (uint32_t)l;
+    kind[i] = k;
+  }
+}
+
+struct NameLenIn {
+  const uint32_t* len;
+  __device__ __forceinline__ uint64_t operator()(uint64_t i) const { return len[i]; }
+};
+
+// One lane: heap[s, s + len) to dst[d, d + len), the source read in aligned
+// words (the word above the last byte may be read: the heap is padded).
+__device__ __forceinline__ void lane_copy(uint8_t* dst, uint64_t d, const uint8_t* __restrict__ heap, uint64_t s,
+                                          uint32_t len) {
+  const uint32_t* hw = reinterpret_cast<const uint32_t*>(heap);
+  uint32_t w = hw[s >> 2];
+  for (uint32_t k = 0; k < len; ++k) {
+    dst[d + k] = (uint8_t)(w >> (8 * (uint32_t)(s & 3)));
+    if ((++s & 3) == 0) w = hw[s >> 2];
+  }
+}
+
+// One wave (every lane calls it with the same arguments): bytes up to the
+// destination's 16-byte boundary and after its last whole vector singly, the
+// vectors between as 16-byte stores -- loaded as one 16-byte word where the
+// source is aligned like the destination, else put together from five aligned
+// 32-bit words.  `dst + d` has the alignment of d.
+__device__ __forceinline__ void wave_copy(uint8_t* dst, uint64_t d, const uint8_t* __restrict__ heap, uint64_t s,
+                                          uint64_t len) {
+  const uint32_t lane = __lane_id();
+  const uint64_t to_vec = (16 - (d & 15)) & 15;
+  const uint64_t head = len < to_vec ? len : to_vec;
+  if (lane < head) dst[d + lane] = heap[s + lane];
+  const uint64_t nv = (len - head) >> 4;
+  const uint64_t d0 = d + head, s0 = s + head;
+  if ((s0 & 15) == 0) {
+    for (uint64_t v = lane; v < nv; v += 64)
+      *reinterpret_cast<uint4*>(dst + d0 + 16 * v) = *reinterpret_cast<const uint4*>(heap + s0 + 16 * v);
+  } else {
+    const uint32_t* hw = reinterpret_cast<const uint32_t*>(heap);
+    const uint32_t sh = 8 * (uint32_t)(s0 & 3);
+    for (uint64_t v = lane; v < nv; v += 64) {
+      const uint64_t a = (s0 + 16 * v) >> 2;
+      const uint32_t w0 = hw[a], w1 = hw[a + 1], w2 = hw[a + 2], w3 = hw[a + 3], w4 = hw[a + 4];
+      uint4 o;
+      o.x = __funnelshift_r(w0, w1, sh);
+      o.y = __funnelshift_r(w1, w2, sh);
+      o.z = __funnelshift_r(w2, w3, sh);
+      o.w = __funnelshift_r(w3, w4, sh);
+      *reinterpret_cast<uint4*>(dst + d0 + 16 * v) = o;
+    }
+  }
+  const uint64_t done = head + 16 * nv;
+  if (lane < len - done) dst[d + done + lane] = heap[s + done + lane];
+}
+
+// The names of a wave's lanes that are longer than kCopyWave, one after the
+// other, each by the whole wave.  Called by every lane of the wave.
+__device__ __forceinline__ void wave_copy_long(bool mine, uint8_t* dst, uint64_t d, const uint8_t* __restrict__ heap,
+                                               uint64_t s, uint64_t len) {
+  uint64_t m = __ballot(mine);
+  while (m) {
+    const int l = __ffsll((unsigned long long)m) - 1;
+    m &= m - 1;
+    const uint64_t dl = ((uint64_t)__shfl((uint32_t)(d >> 32), l, 64) << 32) | __shfl((uint32_t)d, l, 64);
+    const uint64_t sl = ((uint64_t)__shfl((uint32_t)(s >> 32), l, 64) << 32) | __shfl((uint32_t)s, l, 64);
+    const uint64_t ll = ((uint64_t)__shfl((uint32_t)(len >> 32), l, 64) << 32) | __shfl((uint32_t)len, l, 64);
+    wave_copy(dst, dl, heap, sl, ll);
+  }
+}
+
+// out[doff[i] .. doff[i + 1]) = heap[src[i] .. + len[i]) for i < n, nothing
+// written at or past out[cap].  `out` is 16-byte aligned; heap as k_name_match.
+__global__ void __launch_bounds__(kNameBlock) k_name_copy(const uint8_t* __restrict__ heap,
+                                                         const uint64_t* __restrict__ src,
+                                                         const uint32_t* __restrict__ len,
+                                                         const uint64_t* __restrict__ doff, uint64_t n, uint64_t cap,
+                                                         uint8_t* __restrict__ out) {
+  __shared__ uint4 s_img[kFetchVecs];
+  const uint32_t tid = threadIdx.x;
+  const uint64_t tiles = (n + kNameBlock - 1) / kNameBlock;
+  for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const uint64_t i0 = t * kNameBlock;
+    const uint64_t cnt = n - i0 < kNameBlock ? n - i0 : kNameBlock;
+    const uint64_t tb = doff[i0], te_all = doff[i0 + cnt];       // the tile's output bytes (block-uniform)
+    const uint64_t te = te_all < cap ? te_all : cap;
+    if (tb >= te) continue;                                     // nothing to write (block-uniform)
+    uint64_t d = 0, s = 0;
+    uint32_t l = 0;
+    if (tid < cnt) {
+      d = doff[i0 + tid];
+      s = src[i0 + tid];
+      l = len[i0 + tid];
+    }
+    const uint64_t ab = tb & ~15ull;
+    if (te_all - ab <= kFetchStage) {
+      // staged: every name of the tile into the image of out[ab, te_all)
+      uint8_t* img = reinterpret_cast<uint8_t*>(s_img);
+      __syncthreads();                                          // the previous tile's image was written out
+      if (l && l <= kCopyWave) lane_copy(img, d - ab, heap, s, l);
+      wave_copy_long(l > kCopyWave, img, d - ab, heap, s, l);
+      __syncthreads();
+      const uint64_t nvec = (te - ab + 15) >> 4;
+      for (uint64_t v = tid; v < nvec; v += kNameBlock) {
+        const uint64_t g = ab + 16 * v;
+        if (g >= tb && g + 16 <= te) {
+          *reinterpret_cast<uint4*>(out + g) = s_img[v];
+        } else {                                                // an edge vector shared with a neighbour tile / the cap
+          const uint64_t b0 = g > tb ? g : tb, b1 = g + 16 < te ? g + 16 : te;
+          for (uint64_t p = b0; p < b1; ++p) out[p] = img[p - ab];
+        }
+      }
+    } else {
+      // too large for the image: each name straight to the output, cut at cap
+      const uint64_t room = d < cap ? cap - d : 0;
+      const uint64_t lc = l < room ? l : room;
+      if (lc && l <= kCopyWave) lane_copy(out, d, heap, s, (uint32_t)lc);
+      wave_copy_long(l > kCopyWave && lc, out, d, heap, s, lc);
+    }
+  }
+}
+
 }  // namespace
+
+uint64_t node_names(Ctx& c, const uint32_t* h_ids, const uint32_t* d_ids, uint64_t n, uint64_t* off, uint8_t* bytes,
+                    uint64_t cap, uint8_t* kind, uint64_t* n_other) {
+  DAS_CHECK(c.idx.built, DAS_E_NOT_BUILT, "index not built");
+  DAS_CHECK(off && kind, DAS_E_INVALID, "null offset / kind buffer");
+  DAS_CHECK(bytes || !cap, DAS_E_INVALID, "null name buffer");
+  DAS_CHECK(h_ids || d_ids || !n, DAS_E_INVALID, "null id buffer");
+  ensure_name_heap(c);
+  if (n_other) *n_other = 0;
+  off[0] = 0;
+  if (!n) return 0;
+  const NameHeap& h = c.idx.names;
+  hipStream_t s = c.s;
+  DBuf<uint32_t> ids_up(d_ids ? 0 : n, s);
+  if (!d_ids) {
+    DAS_HIP(hipMemcpyAsync(ids_up.p, h_ids, 4 * n, hipMemcpyHostToDevice, s));
+    d_ids = ids_up.p;
+  }
+  DBuf<uint64_t> src(n, s), doff(n + 1, s);
+  DBuf<uint32_t> len(n, s);
+  DBuf<uint8_t> d_kind(n, s);
+  {
+    KScope ks("k_name_locate", 4.0 * n + 4.0 * n * (double)bits_for(h.n_nodes) + 16.0 * n + 13.0 * n);
+    const uint64_t n_listed = h.node_id && h.off && h.bytes ? h.n_nodes : 0;   // (a KB without nodes has no heap)
+    hipLaunchKernelGGL(k_name_locate, G(n), dim3(256), 0, s, d_ids, n, (const uint8_t*)c.idx.cat, c.idx.n_atoms,
+                       (const uint32_t*)h.node_id, n_listed, (const uint64_t*)h.off, h.n_bytes, src.p, len.p,
+                       d_kind.p);
+    DAS_HIP(hipGetLastError());
+  }
+  uint64_t total = 0;
+  {
+    KScope ks("name_fetch_scan", 2.0 * 4.0 * n + 8.0 * n);
+    total = scan_total<uint64_t>(NameLenIn{len.p}, n, doff.p, s);   // read-back 1: the total
+  }
+  const uint64_t k = std::min(total, cap);
+  DBuf<uint8_t> d_out(k, s);
+  if (k) {
+    const uint64_t tiles = (n + kNameBlock - 1) / kNameBlock;
+    KScope ks("k_name_copy", 2.0 * (double)k + 20.0 * n);
+    hipLaunchKernelGGL(k_name_copy, dim3(grid_for(tiles, 1, 8192)), dim3(kNameBlock), 0, s, (const uint8_t*)h.bytes,
+                       (const uint64_t*)src.p, (const uint32_t*)len.p, (const uint64_t*)doff.p, n, k, d_out.p);
+    DAS_HIP(hipGetLastError());
+    DAS_HIP(hipMemcpyAsync(bytes, d_out.p, k, hipMemcpyDeviceToHost, s));
+  }
+  DAS_HIP(hipMemcpyAsync(off, doff.p, 8 * (n + 1), hipMemcpyDeviceToHost, s));
+  DAS_HIP(hipMemcpyAsync(kind, d_kind.p, n, hipMemcpyDeviceToHost, s));
+  DAS_HIP(hipStreamSynchronize(s));                                  // read-back 2: the payload
+  uint64_t other = 0;
+  for (uint64_t i = 0; i < n; ++i) other += kind[i] ? 0 : 1;
+  if (n_other) *n_other = other;
+  return total;
+}
 
 void ensure_name_heap(Ctx& c) {
   DAS_CHECK(c.idx.built, DAS_E_NOT_BUILT, "index not built");

@@ -126,6 +126,11 @@ class HipDB(RelationalDB):
     PREFETCH_MAX_ATOMS = 1 << 26            # host mirrors of prefetch() up to this many atoms
     HEX_DIRECT = 4096                       # hex_of: larger id arrays skip the per-id cache
     SEED_MAX = 1 << 16                      # _pairs: answers up to this size seed the handle cache
+    # get_node_names / answer.names: fewer entries than this take the host loop.  Measured on 10^7 nodes
+    # (profiles/name_fetch.json): a device call costs 0.09 ms; the loop costs 0.095 ms for ONE name as loaded
+    # (two device round trips per name) and 0.7 us per name after prefetch() (0.05 ms at 64, 0.18 ms at 256).
+    NAME_FETCH_MIN = 1
+    NAME_FETCH_MIN_PREFETCHED = 256
 
     def __init__(self, device: int = 0, stream=None, tuple_targets: bool = False,
                  stale_pattern_keys: bool = False):
@@ -177,6 +182,8 @@ class HipDB(RelationalDB):
         self._name_stats = {}           # named type id -> (nodes, name bytes, ascii_only), per load
         self._name_dfas = {}            # (pattern, ascii_only) -> NameDFA or None
         self.name_search_stats = {"device": 0, "host": 0}   # get_matched_node_name calls answered by each path
+        # get_node_names / answer.names columns / get_all_nodes calls answered by each path
+        self.name_fetch_stats = {"device": 0, "host": 0}
         self.miner_stats = {"device": 0, "host": 0}         # halo / pattern_counts calls answered by each path
         self.conjunction_stats = {"device": 0, "host": 0}   # conjunction_counts: combinations counted by each path
         self.mine_stats = {"device": 0, "host": 0}          # mine: calls answered by each path
@@ -637,10 +644,32 @@ class HipDB(RelationalDB):
                 gc.enable()
 
     def get_all_nodes(self, node_type: str, names: bool = False) -> List[str]:
-        """redis_mongo_db.py:254-267"""
+        """redis_mongo_db.py:254-267.  The type's range of the resident name
+        heap answers it (ascending id): the ids through the name matcher
+        with an automaton that accepts every name, the names through
+        das_node_names; no host copy of the per-atom arrays is built.  With
+        DAS_NAME_FETCH=0, and for an index without a name heap, the host
+        mirror answers as before.  `name_fetch_stats` counts the calls."""
         tid = self.type_id.get(node_type)
         if tid is None:
             return []
+        if self._name_fetch_on_device():
+            try:
+                n_nodes = self._name_type_stats(tid)[0]
+                ids = self.ctx.match_node_names(tid, _name_search.ACCEPT_ALL, cap=n_nodes)[0] if n_nodes else None
+            except NotImplementedError:     # no name heap for this index
+                ids = False
+            if ids is not False:
+                self.name_fetch_stats["device"] += 1
+                if ids is None or not ids.size:
+                    return []
+                if not names:
+                    return self.hex_of(ids)
+                out = _lib.decode_names(*self.ctx.node_names(ids=ids))
+                if None in out:
+                    raise RuntimeError("get_all_nodes: the name heap lists an atom that is not a node")
+                return out
+        self.name_fetch_stats["host"] += 1
         dig, cat, _, ty, nl = self._host_mirror()
         sel = np.nonzero((cat == 1) & (ty == tid))[0]
         if names:
@@ -681,6 +710,78 @@ class HipDB(RelationalDB):
             return self.arrays.node_name(int(self._mirror[4][aid]))
         _, _, _, _, nl = self.ctx.atoms_info(np.array([aid], dtype=np.uint32))
         return self.arrays.node_name(int(nl[0]))
+
+    def _name_fetch_on_device(self, n=None):
+        """das_node_names answers unless DAS_NAME_FETCH=0 or the `n` entries
+        asked for are fewer than the host loop is measured to be faster at
+        (NAME_FETCH_MIN; NAME_FETCH_MIN_PREFETCHED once prefetch() has
+        mirrored handles and names on the host)."""
+        if os.environ.get("DAS_NAME_FETCH", "1") == "0":
+            return False
+        if n is None:
+            return True
+        return n >= (self.NAME_FETCH_MIN if self._node_dir is None else self.NAME_FETCH_MIN_PREFETCHED)
+
+    def get_node_names_host(self, handles_or_ids, strict=True):
+        """get_node_names as the loop over get_node_name it replaces."""
+        if isinstance(handles_or_ids, np.ndarray) and handles_or_ids.dtype != object:
+            # an id outside the index has no handle: it stands for itself
+            ids = np.asarray(handles_or_ids).ravel().astype(np.int64)
+            ok = (ids >= 0) & (ids < int(self.ctx.stats().n_atoms))
+            handles = ids.tolist()
+            for i, h in zip(np.flatnonzero(ok).tolist(), self.hex_of(ids[ok].astype(np.uint32))):
+                handles[i] = h
+        else:
+            handles = list(handles_or_ids)
+        out = []
+        for h in handles:
+            try:
+                if not isinstance(h, str):
+                    raise ValueError(f"Invalid handle: {h}")
+                out.append(self.get_node_name(h))
+            except ValueError:
+                if strict:
+                    raise
+                out.append(None)
+        return out
+
+    def get_node_names(self, handles_or_ids, strict=True):
+        """get_node_name (redis_mongo_db.py:281-285) of many atoms at once:
+        handles, or a uint32 array of atom ids as hex_of takes; the names in
+        input order.  An entry that is not a node raises ValueError("Invalid
+        handle: ..."), the first one in input order, as get_node_name does;
+        with strict=False it is None instead.  One das_node_names call: a
+        gather over the resident name heap.  With DAS_NAME_FETCH=0, below
+        NAME_FETCH_MIN entries (NAME_FETCH_MIN_PREFETCHED after prefetch())
+        and for an index without a name heap the loop get_node_names_host
+        answers.  `name_fetch_stats` counts the calls of each path."""
+        by_id = isinstance(handles_or_ids, np.ndarray) and handles_or_ids.dtype != object
+        handles_or_ids = np.asarray(handles_or_ids).ravel() if by_id else list(handles_or_ids)
+        if self._name_fetch_on_device(len(handles_or_ids)):
+            if by_id:
+                if handles_or_ids.dtype.kind not in "iu":
+                    raise ValueError("get_node_names: ids must be integers")
+                ids = handles_or_ids.astype(np.int64)
+                ids[(ids < 0) | (ids > _lib.DAS_NONE)] = _lib.DAS_NONE      # no atom has such an id
+            else:
+                ids = self.ids_of(handles_or_ids)
+                ids[ids < 0] = _lib.DAS_NONE                                # a handle the index does not hold
+            ids = ids.astype(np.uint32)
+            try:
+                off, data, kind = self.ctx.node_names(ids=ids)
+            except NotImplementedError:     # no name heap for this index
+                kind = None
+            if kind is not None:
+                self.name_fetch_stats["device"] += 1
+                if strict and not kind.all():
+                    i = int(np.flatnonzero(kind == 0)[0])
+                    bad = handles_or_ids[i]
+                    if by_id:       # the atom's handle, as get_node_name names it; an id outside the index as it is
+                        bad = self.hex_of(ids[i:i + 1])[0] if int(ids[i]) < int(self.ctx.stats().n_atoms) else int(bad)
+                    raise ValueError(f"Invalid handle: {bad}")
+                return _lib.decode_names(off, data, kind)
+        self.name_fetch_stats["host"] += 1
+        return self.get_node_names_host(handles_or_ids, strict)
 
     def _name_type_stats(self, tid):
         """(nodes, name bytes, ascii_only) of a named type; ascii_only: every

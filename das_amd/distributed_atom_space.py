@@ -222,6 +222,32 @@ class DistributedAtomSpace:
     def get_node_name(self, node_handle: str) -> str:
         return self.db.get_node_name(node_handle)
 
+    def get_node_names(self, handles, strict: bool = True) -> List[str]:
+        """get_node_name of every handle, in order, as one call (on a HipDB a
+        gather over the resident names, HipDB.get_node_names); strict=False
+        puts None where get_node_name would raise."""
+        if hasattr(self.db, "get_node_names"):
+            return self.db.get_node_names(handles, strict=strict)
+        out = []
+        for h in handles:
+            try:
+                out.append(self.db.get_node_name(h))
+            except ValueError:
+                if strict:
+                    raise
+                out.append(None)
+        return out
+
+    def get_mappings(self, query: LogicalExpression, variable: str) -> List[str]:
+        """QueryFlyBase.ipynb's get_mappings as one call: the node name of
+        `variable` in every assignment of the query's answer ([] where the
+        query does not match), in no particular order
+        (PatternMatchingAnswer.names)."""
+        query_answer = PatternMatchingAnswer()
+        if not query.matched(self.db, query_answer):
+            return []
+        return query_answer.names(variable, db=self.db)
+
     # -- pattern miner (notebooks/SimplePatternMiner.ipynb cells 6 and 5) ----
     def halo(self, seeds: List[str], length: int = 2):
         """The halo walk around the seed handles: a miner.Halo

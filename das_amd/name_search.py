@@ -99,6 +99,12 @@ class NameDFA(NamedTuple):
         return bool(self.accept[int(self.next[s * k + self.eot_class])])
 
 
+# One accepting state and one class: every name matches (HipDB.get_all_nodes
+# lists a type's node ids through the matcher with it).
+ACCEPT_ALL = NameDFA(1, 1, 0, 0, np.zeros(256, dtype=np.uint8), np.zeros(1, dtype=np.uint16),
+                     np.ones(1, dtype=np.uint8))
+
+
 class _Decline(Exception):
     pass
 

@@ -771,6 +771,91 @@ class PatternMatchingAnswer:
             return 0
         return self._db.rel_count(self._relation())
 
+    def names(self, variable=None, strict=True, db=None):
+        """The node names of the answer's values, get_node_name of each in
+        one call: for one variable a list, one name per assignment; with no
+        variable a dict variable -> list, the lists aligned row by row.  Row
+        order is unspecified (the tables' row order on the device path, set
+        order on the host path).  A value that is not a node raises
+        ValueError("Invalid handle: ..."), or is None with strict=False; a
+        variable the answer does not bind raises KeyError.
+
+        Device path -- the answer still holds its device relation, every
+        local table is ordered and the DB is a HipDB: one das_node_names
+        call per column, read from the table where it lies (no fetch, no
+        handle string, no Assignment object).  Everything else (unordered or
+        composite tables, hand-set assignments, a sharded DB,
+        DAS_NAME_FETCH=0, an index without a name heap, fewer rows than
+        HipDB.NAME_FETCH_MIN) runs names_host.  `db.name_fetch_stats` counts
+        the device calls and the host runs.  `db`: the DB
+        of an answer whose assignments were set by hand."""
+        db = db if db is not None else self._db
+        if db is None:
+            if self._py is None or self._py:
+                raise ValueError("names: the answer holds no database")
+            return {} if variable is None else []
+        if self._rel is not None and db is self._db and isinstance(db, HipDB) and db._name_fetch_on_device():
+            tables = [t for t in db.rel_local_tables(self._rel) if t.nrows]
+            if (all(t.kind == _lib.TABLE_ORDERED for t in tables)
+                    and db._name_fetch_on_device(sum(t.nrows for t in tables))):
+                try:
+                    return _names_device(db, tables, variable, strict)
+                except NotImplementedError:     # no name heap for this index
+                    pass
+        if hasattr(db, "name_fetch_stats"):
+            db.name_fetch_stats["host"] += 1
+        return names_host(db, self, variable, strict)
+
+
+def names_host(db, answer, variable=None, strict=True):
+    """The definition of PatternMatchingAnswer.names, over any DBInterface:
+    [db.get_node_name(a.mapping[variable]) for a in answer.assignments], the
+    notebooks' get_mappings loop; with no variable, that list for every
+    variable an assignment binds, over one pass of the assignments.  An
+    assignment without a `mapping` (unordered, composite) raises
+    AttributeError, as that loop does."""
+    rows = list(answer.assignments)
+    if variable is not None:
+        variables = [variable]
+    else:
+        variables = sorted(set().union(*[a.variables for a in rows])) if rows else []
+    out = {v: [] for v in variables}
+    for a in rows:
+        for v in variables:
+            h = a.mapping[v]
+            try:
+                out[v].append(db.get_node_name(h))
+            except ValueError:
+                if strict:
+                    raise
+                out[v].append(None)
+    return out[variable] if variable is not None else out
+
+
+def _names_device(db, tables, variable, strict):
+    """names over ordered device tables: das_node_names per column."""
+    if variable is not None:
+        variables = [variable]
+    else:
+        variables = sorted({_var_name(v) for t in tables for v in t.vars})
+    out = {v: [] for v in variables}
+    for t in tables:
+        bound = [_var_name(v) for v in t.vars]
+        for v in variables:
+            if v not in bound:
+                raise KeyError(v)
+    for t in tables:
+        bound = [_var_name(v) for v in t.vars]
+        for v in variables:
+            c = bound.index(v)
+            off, data, kind = db.ctx.node_names(table=t, col=c)
+            db.name_fetch_stats["device"] += 1
+            if strict and not kind.all():
+                row = int(np.flatnonzero(kind == 0)[0])
+                raise ValueError(f"Invalid handle: {db.hex_of(t.fetch(row, 1)[c])[0]}")
+            out[v] += _lib.decode_names(off, data, kind)
+    return out[variable] if variable is not None else out
+
 
 try:
     from .. import _assign          # C builder of the answer's Assignment objects (csrc/pyassign.c)

@@ -242,6 +242,24 @@ int das_match_node_names(das_ctx_t* ctx, uint32_t type_id, const das_name_dfa_t*
  * every name byte is < 0x80 and not '\n' (builds the name heap if need be). */
 int das_node_name_stats(das_ctx_t* ctx, uint32_t type_id, uint64_t* n_nodes, uint64_t* n_bytes, uint32_t* ascii_only);
 
+/* ---- node-name fetch (get_node_name in bulk, redis_mongo_db.py:281-285) ---- */
+#define DAS_NAME_COPY_WAVE 64 /* a name longer than this many bytes is copied by a whole wave */
+/* The names of n atoms, in input order, one entry per input (an id that
+ * repeats is answered each time).  The inputs are the n host ids `ids`, or --
+ * `table` not NULL, `ids` ignored -- rows [row0, row0 + n) of column `col` of
+ * a table, read where they lie on the device.  off[i] .. off[i + 1] are the
+ * bytes of entry i in `bytes` (UTF-8 as loaded, back to back, off[n] = the
+ * total); kind[i] = 1 for a node, 0 for anything else (a link, DAS_NONE, an id
+ * >= n_atoms), whose entry is empty; *n_other = the number of those.
+ * *n_bytes = the total whatever `cap` is; min(total, cap) bytes are copied to
+ * `bytes` and nothing is written past `cap` (as das_match_node_names' cap: a
+ * caller that guessed too small calls again with the total).  off (n + 1) and
+ * kind (n) are filled in full.  Builds the name heap if need be (see
+ * das_match_node_names). */
+int das_node_names(das_ctx_t* ctx, const uint32_t* ids, uint64_t n, const das_table_t* table, int32_t col,
+                   uint64_t row0, uint64_t* off, uint8_t* bytes, uint64_t cap, uint8_t* kind, uint64_t* n_bytes,
+                   uint64_t* n_other);
+
 /* ---- pattern miner (notebooks/SimplePatternMiner.ipynb cells 6 and 5) ----- */
 #define DAS_HALO_MAX_LEVELS 8
 #define DAS_HALO_BLOCK_ENTRIES 1024 /* incoming-list entries one workgroup marks per pass */
