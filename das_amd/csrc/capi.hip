@@ -713,10 +713,16 @@ int das_partition(das_ctx_t* ctx, const das_table_t* t, const int32_t* key_vars,
 
 int das_table_gather(das_ctx_t* ctx, const das_table_t* t, const uint32_t* idx, uint64_t n, das_table_t** out) {
   return guarded(ctx, [&] {
-    for (uint64_t i = 0; i < n; ++i) DAS_CHECK(idx[i] < t->t.nrows, das::DAS_E_INVALID, "gather index out of range");
+    bool ascending = true;                        // the source's row order survives only ascending indices
+    for (uint64_t i = 0; i < n; ++i) {
+      DAS_CHECK(idx[i] < t->t.nrows, das::DAS_E_INVALID, "gather index out of range");
+      if (i && idx[i] < idx[i - 1]) ascending = false;
+    }
     das::DBuf<uint32_t> d(n ? n : 1, ctx->c.s);
     if (n) DAS_HIP(hipMemcpyAsync(d.p, idx, 4 * n, hipMemcpyHostToDevice, ctx->c.s));
-    *out = wrap(das::gather_table(ctx->c, t->t, d.p, n));
+    auto g = das::gather_table(ctx->c, t->t, d.p, n);
+    if (!ascending) g->sorted_col = -1;
+    *out = wrap(std::move(g));
     DAS_HIP(hipStreamSynchronize(ctx->c.s));      // `idx` is caller memory
   });
 }

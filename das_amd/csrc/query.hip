@@ -1691,16 +1691,22 @@ __global__ void k_gather_ranges(ColSet src, const uint64_t* prefix, const uint64
 std::unique_ptr<Table> gather_ranges(Ctx& c, const Table& a, const uint64_t* begin, const uint64_t* end,
                                      uint32_t n_ranges) {
   std::vector<uint64_t> h(2 * (uint64_t)n_ranges + 1, 0);
-  uint64_t m = 0;
+  uint64_t m = 0, last = 0;
+  bool ascending = true;                             // the source's row order survives only ascending ranges
   for (uint32_t i = 0; i < n_ranges; ++i) {
     DAS_CHECK(begin[i] <= end[i] && end[i] <= a.nrows, DAS_E_INVALID, "gather range outside the table");
     h[i] = m;                                        // prefix
     h[n_ranges + 1 + i] = begin[i];
     m += end[i] - begin[i];
+    if (end[i] > begin[i]) {
+      if (begin[i] < last) ascending = false;
+      last = end[i] - 1;
+    }
   }
   h[n_ranges] = m;
   auto t = new_table_like(c, a, m);
   t->nrows = m;
+  if (!ascending) t->sorted_col = -1;
   if (m && a.ncols) {
     DBuf<uint64_t> d(h.size(), c.s);
     // from pageable memory: the runtime stages it before returning, so no
@@ -5105,7 +5111,7 @@ std::unique_ptr<Table> antijoin(Ctx& c, const Table& A, const Table& T) {
   auto Ts = gather_table(c, T, perm.p, T.nrows);
   ColSet tks = cols_of(*Ts), ak{};
   ak.n = T.ncols;
-  for (int k = 0; k < T.ncols; ++k) ak.c[k] = A.col(A.kind == DAS_TABLE_ORDERED ? colof(A, T.vars[k]) : k);
+  for (int k = 0; k < T.ncols; ++k) ak.c[k] = A.col(colof(A, T.vars[k]));   // both operands are ordered here
   DBuf<uint32_t> keep(A.nrows, c.s);
   {
     ProfScope ps(c, "k_anti_flags", 4.0 * A.nrows * (T.ncols + 1));

@@ -18,86 +18,8 @@ import torch.multiprocessing as mp
 
 from das_amd.parallel import handle_owner
 from oracle import das_oracle as O
-
-ORDERED, UNORDERED, COMPOSITE = 0, 1, 2
-
-
-class NTable:
-    def __init__(self, kind, vars_, rows, members=None):
-        self.kind = kind
-        self.vars = tuple(vars_)
-        self.members = tuple(members) if kind == COMPOSITE else None
-        self.rows = np.asarray(rows, dtype=np.uint32).reshape(-1, len(vars_))
-
-    @property
-    def nrows(self):
-        return self.rows.shape[0]
-
-    @property
-    def schema(self):
-        return (self.kind, self.vars, self.members)
-
-    def fetch(self):
-        return self.rows.T.copy()
-
-
-# ---- composite rows <-> the oracle's row model (ints as variables and values)
-def _parts(t):
-    """(ordered var list or None, [member var lists]) of a table schema."""
-    if t.kind == ORDERED:
-        return list(t.vars), []
-    if t.kind == UNORDERED:
-        return None, [list(t.vars)]
-    o = [v for v, m in zip(t.vars, t.members) if m < 0]
-    mem = {}
-    for v, m in zip(t.vars, t.members):
-        if m >= 0:
-            mem.setdefault(m, []).append(v)
-    return (o or None), [mem[m] for m in sorted(mem)]
-
-
-def _to_oracle(t, r):
-    r = [int(x) for x in r]
-    if t.kind == ORDERED:
-        return O.o_row(dict(zip(t.vars, r)))
-    if t.kind == UNORDERED:
-        return O.u_row(t.vars, r)
-    o, mems = _parts(t)
-    k = len(o) if o else 0
-    orow = O.o_row(dict(zip(o, r[:k]))) if o else None
-    us = []
-    for mv in mems:
-        us.append(O.u_row(mv, r[k:k + len(mv)]))
-        k += len(mv)
-    return ("C", orow, us)
-
-
-def _join_schema(a, b):
-    """Output schema of the CompositeAssignment join (composite.hip)."""
-    if a.kind == ORDERED or (a.kind == UNORDERED and b.kind == COMPOSITE):
-        x, y = b, a
-    else:
-        x, y = a, b
-    xo, xm = _parts(x)
-    yo, ym = _parts(y)
-    o = set(xo or [])
-    if y.kind != UNORDERED and not (xo and not yo):
-        o |= set(yo or [])
-    mems = xm + (ym if y.kind != ORDERED else [])
-    vars_ = sorted(o) + [v for m in mems for v in m]
-    members = [-1] * len(o) + [i for i, m in enumerate(mems) for _ in m]
-    return vars_, members
-
-
-def _from_oracle(vars_, members, rows):
-    out = []
-    for r in rows:
-        vals = dict(r[1][1]) if r[1] is not None else {}
-        line = [vals[v] for v, m in zip(vars_, members) if m < 0]
-        for u in r[2]:
-            line += list(u[2])
-        out.append(line)
-    return NTable(COMPOSITE, vars_, np.array(out, np.uint32).reshape(-1, len(vars_)), members)
+from tests import table_model as TM
+from tests.table_model import ORDERED, UNORDERED, NTable
 
 
 class NRel:
@@ -227,79 +149,34 @@ class NumpyLocal:
         return NTable(kind, vars_, np.zeros((0, len(vars_)), np.uint32), members)
 
     def partition(self, t, key_vars, nparts):
-        cols = [t.vars.index(v) for v in key_vars] if key_vars else list(range(len(t.vars)))
-        h = np.zeros(t.nrows, dtype=np.uint64)
-        for c in cols:
-            h = h * np.uint64(1000003) + t.rows[:, c].astype(np.uint64)
-        dest = (h % np.uint64(nparts)).astype(np.int64)
-        order = np.argsort(dest, kind="stable")
-        counts = np.bincount(dest, minlength=nparts).astype(np.uint64)
-        return NTable(t.kind, t.vars, t.rows[order], t.members), counts
+        return TM.partition(t, key_vars, nparts)
 
     def dedup(self, t):
-        if t.nrows == 0:
-            return t
-        return NTable(t.kind, t.vars, np.unique(t.rows, axis=0))
+        return TM.dedup(t)
 
     def concat(self, ts):
-        return NTable(ts[0].kind, ts[0].vars, np.concatenate([t.rows for t in ts]), ts[0].members)
+        return TM.concat(ts)
 
     def set_dedup(self, ts):
-        seen, out = set(), []
-        for t in ts:
-            keep = []
-            for r in t.rows:
-                k = O.ident(_to_oracle(t, r))
-                if k not in seen:
-                    seen.add(k)
-                    keep.append(r)
-            out.append(NTable(t.kind, t.vars, np.array(keep, np.uint32).reshape(-1, len(t.vars)), t.members))
-        return out
+        return TM.set_dedup(ts)
 
     def set_minus(self, a, b):
-        gone = {O.ident(_to_oracle(t, r)) for t in b for r in t.rows}
-        return [NTable(t.kind, t.vars, np.array([r for r in t.rows if O.ident(_to_oracle(t, r)) not in gone],
-                                                np.uint32).reshape(-1, len(t.vars)), t.members) for t in a]
+        return TM.set_minus(a, b)
 
     def slice(self, t, lo, hi):
         return NTable(t.kind, t.vars, t.rows[lo:hi], t.members)
 
     def gather_rows(self, t, idx):
-        return NTable(t.kind, t.vars, t.rows[np.asarray(idx, dtype=np.int64)], t.members)
+        return TM.gather_rows(t, idx)
 
     def gather_ranges(self, t, begin, end):
-        idx = [np.arange(int(b), int(e)) for b, e in zip(begin, end)]
-        return self.gather_rows(t, np.concatenate(idx) if idx else np.zeros(0, np.int64))
+        return TM.gather_ranges(t, begin, end)
 
     def join(self, a, b, no_overload=False):
-        if a.kind != ORDERED or b.kind != ORDERED:
-            vars_, members = _join_schema(a, b)
-            rb = [_to_oracle(b, r) for r in b.rows]
-            out = [j for r in a.rows for y in rb for j in [O.join(_to_oracle(a, r), y)] if j is not None]
-            return _from_oracle(vars_, members, out)
-        shared = sorted(set(a.vars) & set(b.vars))
-        uni = sorted(set(a.vars) | set(b.vars))
-        idx = {}
-        for r in b.rows:
-            idx.setdefault(tuple(r[b.vars.index(v)] for v in shared), []).append(r)
-        out = []
-        for r in a.rows:
-            for s in idx.get(tuple(r[a.vars.index(v)] for v in shared), []):
-                m = {v: r[a.vars.index(v)] for v in a.vars}
-                m.update({v: s[b.vars.index(v)] for v in b.vars})
-                out.append([m[v] for v in uni])
-        return NTable(ORDERED, uni, np.array(out, np.uint32).reshape(-1, len(uni)))
+        return TM.join(a, b, no_overload)
 
     def antijoin(self, a, t):
-        if a.kind != ORDERED or t.kind != ORDERED:
-            rt = [_to_oracle(t, r) for r in t.rows]
-            keep = [r for r in a.rows if all(O.check_negation(_to_oracle(a, r), x) for x in rt)]
-            return NTable(a.kind, a.vars, np.array(keep, np.uint32).reshape(-1, len(a.vars)), a.members)
-        if not set(t.vars) <= set(a.vars):
-            return a
-        bad = {tuple(r) for r in t.rows}
-        keep = [r for r in a.rows if tuple(r[a.vars.index(v)] for v in t.vars) not in bad]
-        return NTable(a.kind, a.vars, np.array(keep, np.uint32).reshape(-1, len(a.vars)))
+        return TM.antijoin(a, t)
 
     # collective staging (CPU tensors for gloo)
     def xfer_tensor(self, arr):
