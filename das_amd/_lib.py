@@ -80,6 +80,8 @@ class das_name_dfa_t(C.Structure):
 NAME_STAGE_BYTES = 16384          # DAS_NAME_STAGE_BYTES: name bytes of one tile the matcher stages in LDS
 NAME_COPY_WAVE = 64               # DAS_NAME_COPY_WAVE: a longer name is copied by a whole wave
 NAME_FETCH_GUESS = 32             # Context.node_names: bytes per name of the first call's capacity
+DOC_MAX_DEPTH = 16                # DAS_DOC_MAX_DEPTH: levels of a deep representation das_atoms_json renders
+DOC_GUESS = 512                   # Context.atoms_json: bytes per root of the first call's capacity
 HALO_MAX_LEVELS = 8               # DAS_HALO_MAX_LEVELS
 HALO_BLOCK_ENTRIES = 1024         # DAS_HALO_BLOCK_ENTRIES: incoming-list entries one workgroup marks per pass
 PC_CHUNK_ROWS = 1024              # DAS_PC_CHUNK_ROWS: index rows one wave counts per step of a (1,2)-grounded template
@@ -131,6 +133,9 @@ _SIGS = {
     "das_match_node_names": (C.c_int, [P, C.c_uint32, P, P, C.c_uint64, P]),
     "das_node_name_stats": (C.c_int, [P, C.c_uint32, P, P, P]),
     "das_node_names": (C.c_int, [P, P, C.c_uint64, P, C.c_int32, C.c_uint64, P, P, C.c_uint64, P, P, P]),
+    "das_atoms_json": (C.c_int, [P, P, C.c_uint64, P, C.c_int32, C.c_uint64, C.c_uint32, P, P, C.c_uint32, P,
+                                 C.c_uint64, P, P, P]),
+    "das_links_outgoing": (C.c_int, [P, P, C.c_uint64, P, C.c_int32, C.c_uint64, P, P, C.c_uint64, P, P, P]),
     "das_halo_expand": (C.c_int, [P, P, C.c_uint64, C.c_uint32, P, P]),
     "das_pattern_counts": (C.c_int, [P, P, P, C.c_uint64, C.POINTER(P)]),
     "das_conjunction_counts": (C.c_int, [P, P, C.c_uint64, P, C.c_uint64, C.c_uint32, P]),
@@ -662,6 +667,95 @@ class Context:
                 break
             cap, guess = total.value, False
         return off, buf[:min(total.value, cap)], kind[:n]
+
+    @staticmethod
+    def _entries(what, ids, table, col, row0, nrows):
+        """The entries of a document call as its first arguments: (ids array
+        or None, n, table handle or None, col, row0)."""
+        if (ids is None) == (table is None):
+            raise ValueError(f"{what}: give either ids or a table")
+        if table is None:
+            ids = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32).ravel())
+            return ids, ids.size, None, 0, 0
+        col, row0 = int(col), int(row0)
+        if not 0 <= col < len(table.vars):
+            raise ValueError(f"{what}: bad column")
+        n = table.nrows - row0 if nrows is None else int(nrows)
+        if row0 < 0 or row0 > table.nrows or n < 0 or n > table.nrows - row0:
+            raise ValueError(f"{what}: rows out of range")
+        return None, n, table.h, col, row0
+
+    def atoms_json(self, type_json, type_json_off, ids=None, table=None, col=0, row0=0, nrows=None, as_list=True,
+                   cap=None, out=None):
+        """(bytes, total, n_other, n_bad_utf8) of das_atoms_json: the
+        json.dumps(..., indent=4) text of the deep representations of `ids`
+        (host uint32 atom ids) or of rows of a device Table column, as a
+        uint8 array of min(total, cap) bytes.  type_json / type_json_off:
+        json.dumps of every named type's name back to back (uint8) and their
+        n_types + 1 offsets (uint64).  cap: copy at most that many bytes
+        (default: a guess from the calls before, and a second call with the
+        total where it was short); out: a uint8 array to copy into.  None
+        instead of the tuple where the documents nest deeper than
+        DOC_MAX_DEPTH levels (DAS_ERR_LIMIT)."""
+        ids, n, th, col, row0 = self._entries("atoms_json", ids, table, col, row0, nrows)
+        tj = np.ascontiguousarray(type_json, dtype=np.uint8)
+        toff = np.ascontiguousarray(type_json_off, dtype=np.uint64)
+        if toff.size < 1 or int(toff[-1]) > tj.size:
+            raise ValueError("atoms_json: type texts shorter than their offsets say")
+        if out is not None:
+            if out.dtype != np.uint8 or not out.flags.c_contiguous or out.ndim != 1:
+                raise ValueError("atoms_json: out must be a contiguous uint8 array")
+            if cap is None:
+                cap = out.size
+            elif int(cap) > out.size:
+                raise ValueError("atoms_json: cap exceeds the out buffer")
+        guess = cap is None
+        per_root = getattr(self, "_doc_guess", DOC_GUESS)
+        cap = int(per_root * n) + 256 if guess else int(cap)
+        if cap < 0:
+            raise ValueError("atoms_json: negative cap")
+        total, other, bad = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        while True:
+            buf = out if out is not None else np.empty(max(cap, 1), dtype=np.uint8)
+            rc = lib().das_atoms_json(self.h, ptr(ids) if n and ids is not None else None, n, th, col, row0,
+                                      1 if as_list else 0, ptr(tj), ptr(toff), toff.size - 1, ptr(buf), cap,
+                                      C.byref(total), C.byref(other), C.byref(bad))
+            if rc == ERR_LIMIT:
+                return None
+            check(rc, self.h)
+            if not guess or total.value <= cap:
+                break
+            cap, guess = total.value, False
+        if n and not other.value and not bad.value:
+            self._doc_guess = max(DOC_GUESS, 1.25 * total.value / n)     # the next call's guess: this one's density
+        return buf[:min(total.value, cap)], total.value, other.value, bad.value
+
+    def links_outgoing(self, ids=None, table=None, col=0, row0=0, nrows=None, cap=None):
+        """(off, targets, ctype, kind) of das_links_outgoing: the outgoing
+        sets of `ids` (host uint32 atom ids) or of rows of a device Table
+        column, in input order.  off: uint64 [n + 1] (off[n] = the true
+        total), targets: uint32 ids back to back, ctype: uint32 [n]
+        composite-type id of a link (DAS_NONE otherwise), kind: uint8 [n]
+        category (0 other / no atom, 1 node, 2 link, 3 link of another
+        shard).  cap: copy at most that many targets (default: a guess, and
+        a second call with the total where it was short)."""
+        ids, n, th, col, row0 = self._entries("links_outgoing", ids, table, col, row0, nrows)
+        guess = cap is None
+        cap = 3 * n + 64 if guess else int(cap)
+        if cap < 0:
+            raise ValueError("links_outgoing: negative cap")
+        off = np.zeros(n + 1, dtype=np.uint64)
+        ctype = np.zeros(max(n, 1), dtype=np.uint32)
+        kind = np.zeros(max(n, 1), dtype=np.uint8)
+        total = C.c_uint64()
+        while True:
+            tg = np.empty(max(cap, 1), dtype=np.uint32)
+            check(lib().das_links_outgoing(self.h, ptr(ids) if n and ids is not None else None, n, th, col, row0,
+                                           ptr(off), ptr(tg), cap, C.byref(total), ptr(ctype), ptr(kind)), self.h)
+            if not guess or total.value <= cap:
+                break
+            cap, guess = total.value, False
+        return off, tg[:min(total.value, cap)], ctype[:n], kind[:n]
 
     def halo_expand(self, seed_ids, levels):
         """(links, atoms): per level one-column Tables of ascending ids, the

@@ -542,6 +542,36 @@ int das_node_names(das_ctx_t* ctx, const uint32_t* ids, uint64_t n, const das_ta
   });
 }
 
+// the ids of a document call: rows [row0, row0 + n) of a table column where they lie, else null (the host ids)
+static const uint32_t* doc_column(const das_table_t* table, int32_t col, uint64_t row0, uint64_t n) {
+  if (!table) return nullptr;
+  DAS_CHECK(col >= 0 && col < table->t.ncols, das::DAS_E_INVALID, "bad column");
+  DAS_CHECK(row0 <= table->t.nrows && n <= table->t.nrows - row0, das::DAS_E_INVALID, "rows out of range");
+  return table->t.col(col) + row0;
+}
+
+int das_atoms_json(das_ctx_t* ctx, const uint32_t* ids, uint64_t n, const das_table_t* table, int32_t col,
+                   uint64_t row0, uint32_t as_list, const uint8_t* type_json, const uint64_t* type_json_off,
+                   uint32_t n_types, uint8_t* out, uint64_t cap, uint64_t* n_bytes, uint64_t* n_other,
+                   uint64_t* n_bad_utf8) {
+  return guarded(ctx, [&] {
+    DAS_CHECK(n_bytes, das::DAS_E_INVALID, "null argument");
+    const uint32_t* d_ids = doc_column(table, col, row0, n);
+    *n_bytes = das::atoms_json(ctx->c, table ? nullptr : ids, d_ids, n, as_list, type_json, type_json_off, n_types,
+                               out, cap, n_other, n_bad_utf8);
+  });
+}
+
+int das_links_outgoing(das_ctx_t* ctx, const uint32_t* ids, uint64_t n, const das_table_t* table, int32_t col,
+                       uint64_t row0, uint64_t* off, uint32_t* targets, uint64_t cap, uint64_t* n_targets,
+                       uint32_t* ctype, uint8_t* kind) {
+  return guarded(ctx, [&] {
+    DAS_CHECK(n_targets, das::DAS_E_INVALID, "null argument");
+    const uint32_t* d_ids = doc_column(table, col, row0, n);
+    *n_targets = das::links_outgoing(ctx->c, table ? nullptr : ids, d_ids, n, off, targets, cap, ctype, kind);
+  });
+}
+
 int das_halo_expand(das_ctx_t* ctx, const uint32_t* seed_ids, uint64_t n_seeds, uint32_t levels,
                     das_table_t** links_out, das_table_t** atoms_out) {
   return guarded(ctx, [&] {

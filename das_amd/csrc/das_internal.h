@@ -384,6 +384,23 @@ uint64_t match_node_names(Ctx& c, uint32_t type_id, const das_name_dfa_t& d, uin
 uint64_t node_names(Ctx& c, const uint32_t* h_ids, const uint32_t* d_ids, uint64_t n, uint64_t* off, uint8_t* bytes,
                     uint64_t cap, uint8_t* kind, uint64_t* n_other);
 
+// docs.hip: atom documents in bulk (das_atoms_json, das_links_outgoing)
+// json.dumps(deep representations, indent=4) of the n roots at d_ids (device)
+// or, d_ids null, at h_ids (host) as bytes: the list dump (as_list 1) or the
+// one root alone (as_list 0, n == 1); type_json: each named type's name as
+// JSON text, n_types + 1 offsets (host).  Returns the total; min(total, cap)
+// bytes copied to `out`.  *n_other: visited entries that are no node and no
+// link, *n_bad_utf8: malformed name bytes (either non-zero: text unspecified).
+// Throws DAS_E_LIMIT beyond DAS_DOC_MAX_DEPTH levels.
+uint64_t atoms_json(Ctx& c, const uint32_t* h_ids, const uint32_t* d_ids, uint64_t n, uint32_t as_list,
+                    const uint8_t* type_json, const uint64_t* type_json_off, uint32_t n_types, uint8_t* out,
+                    uint64_t cap, uint64_t* n_other, uint64_t* n_bad_utf8);
+// outgoing sets of n entries: off[n + 1], min(total, cap) target ids back to
+// back, each entry's composite-type id (kNone unless a link) and category (0
+// also for an id >= n_atoms), all host arrays; returns the total
+uint64_t links_outgoing(Ctx& c, const uint32_t* h_ids, const uint32_t* d_ids, uint64_t n, uint64_t* off,
+                        uint32_t* targets, uint64_t cap, uint32_t* ctype, uint8_t* kind);
+
 // miner.hip: SimplePatternMiner's bulk steps (das_halo_expand, das_pattern_counts)
 // links[l] / atoms[l], l < levels: the links first found at level l (arity 2
 // or 3, type not black-listed, holding a frontier atom) and the targets of

@@ -13,6 +13,7 @@ binding tables (`Relation`).
 """
 import gc
 import itertools
+import json
 import os
 import re
 from typing import Any, List, Tuple
@@ -79,6 +80,11 @@ class RelationalDB(DBInterface):
         (no reference counterpart: RedisMongoDB.prefetch caches types only)."""
 
 
+def _copy_template(tpl):
+    """A link's template (nested lists of type names) with list objects of its own."""
+    return [_copy_template(t) for t in tpl] if isinstance(tpl, list) else tpl
+
+
 def _group(tables):
     g = {}
     for t in tables:
@@ -131,6 +137,14 @@ class HipDB(RelationalDB):
     # (two device round trips per name) and 0.7 us per name after prefetch() (0.05 ms at 64, 0.18 ms at 256).
     NAME_FETCH_MIN = 1
     NAME_FETCH_MIN_PREFETCHED = 256
+    # atoms_json / get_atoms_as_dicts: fewer atoms than this take the per-atom host walk.  Measured on the bench's
+    # FlyBase KB (profiles/atom_docs.json): for ONE link of arity 3 the device calls take 0.14 ms
+    # (JSON) and 0.20 ms (ATOM_INFO), the walk 0.39 and 0.47 ms as loaded and no less after prefetch().  A call
+    # whose atoms are all nodes takes the walk below ATOM_DOCS_MIN_NODES of them: ONE node is one round trip there
+    # (0.09 / 0.08 ms) against 0.11 / 0.28 ms on the device.
+    ATOM_DOCS_MIN = 1
+    ATOM_DOCS_MIN_PREFETCHED = 1
+    ATOM_DOCS_MIN_NODES = 2
 
     def __init__(self, device: int = 0, stream=None, tuple_targets: bool = False,
                  stale_pattern_keys: bool = False):
@@ -187,6 +201,9 @@ class HipDB(RelationalDB):
         self.miner_stats = {"device": 0, "host": 0}         # halo / pattern_counts calls answered by each path
         self.conjunction_stats = {"device": 0, "host": 0}   # conjunction_counts: combinations counted by each path
         self.mine_stats = {"device": 0, "host": 0}          # mine: calls answered by each path
+        self.atom_docs_stats = {"device": 0, "host": 0}     # atoms_json / get_atoms_as_dicts: calls of each path
+        self._type_json = None          # das_atoms_json's type texts, per load
+        self._template_cache = {}       # composite-type id -> template of its links, per load
 
     def __repr__(self):
         return "<HipDB>"
@@ -215,6 +232,8 @@ class HipDB(RelationalDB):
         self._node_dir = None
         self._stale = None
         self._name_stats = {}
+        self._type_json = None
+        self._template_cache = {}
 
     def load_metta(self, texts):
         self.load_arrays(_loader.parse_metta(texts).finish())
@@ -984,6 +1003,147 @@ class HipDB(RelationalDB):
         if cat[0] == 1:
             return {"type": tname, "name": self.arrays.node_name(int(nl[0]))}
         return {"type": tname, "targets": [self._deep(int(x)) for x in self.ctx.link_targets(aid)]}
+
+    # ------------------------------------------- atom documents in bulk (docs.hip)
+    def _atom_docs_on_device(self, handles):
+        """The device calls answer unless DAS_ATOM_DOCS=0 or the atoms asked
+        for are fewer than the host walk is measured to be faster at
+        (ATOM_DOCS_MIN; ATOM_DOCS_MIN_PREFETCHED once prefetch() has mirrored
+        the handles on the host; ATOM_DOCS_MIN_NODES where every handle is a
+        node's: the walk is then one round trip per atom)."""
+        if os.environ.get("DAS_ATOM_DOCS", "1") == "0":
+            return False
+        n = len(handles)
+        if n < self.ATOM_DOCS_MIN_NODES and not isinstance(handles, np.ndarray) and \
+                all(self._lookup(h)[1] == 1 for h in handles):
+            return False
+        return n >= (self.ATOM_DOCS_MIN if self._node_dir is None else self.ATOM_DOCS_MIN_PREFETCHED)
+
+    def _doc_ids(self, handles_or_ids):
+        """(entries as a list or id array, by_id, int64 ids with -1 for an
+        absent handle) of a document call."""
+        by_id = isinstance(handles_or_ids, np.ndarray) and handles_or_ids.dtype != object
+        if by_id:
+            entries = np.asarray(handles_or_ids).ravel()
+            if entries.dtype.kind not in "iu":
+                raise ValueError("atom documents: ids must be integers")
+            return entries, True, entries.astype(np.int64)
+        entries = list(handles_or_ids)
+        return entries, False, self.ids_of(entries)
+
+    def _type_json_texts(self):
+        """json.dumps of every named type's name back to back, and the
+        offsets (das_atoms_json's type texts; made once per load)."""
+        if self._type_json is None:
+            texts = [json.dumps(t).encode("ascii") for t in self.arrays.type_names]
+            off = np.zeros(len(texts) + 1, dtype=np.uint64)
+            if texts:
+                off[1:] = np.cumsum([len(t) for t in texts], dtype=np.uint64)
+            self._type_json = (np.frombuffer(b"".join(texts), dtype=np.uint8), off)
+        return self._type_json
+
+    def atoms_json_host(self, handles_or_ids, as_list=True):
+        """atoms_json as the per-atom walk it replaces (_deep: two device
+        round trips per visited atom)."""
+        entries, by_id, _ = self._doc_ids(handles_or_ids)
+        if by_id:
+            docs = [self._deep(int(i)) for i in entries]
+        else:
+            docs = [self.get_atom_as_deep_representation(h) for h in entries]
+        if not as_list and len(docs) != 1:
+            raise ValueError("atoms_json: one atom unless as_list")
+        return json.dumps(docs if as_list else docs[0], sort_keys=False, indent=4)
+
+    def atoms_json(self, handles_or_ids, as_list=True) -> str:
+        """json.dumps(deep representations, sort_keys=False, indent=4) of many
+        atoms -- handles, or a uint32 array of atom ids -- as one text: the
+        dump of the list (as_list) or of the one atom alone.  A handle the KB
+        does not hold raises ValueError("Invalid handle: ..."), the first in
+        input order, as get_atom_as_deep_representation does.  One
+        das_atoms_json call renders the text on the device.  The host walk
+        atoms_json_host answers with DAS_ATOM_DOCS=0, below ATOM_DOCS_MIN
+        atoms (ATOM_DOCS_MIN_PREFETCHED after prefetch(); ATOM_DOCS_MIN_NODES
+        where all are nodes), for an index
+        without a name heap, where an entry at any depth is neither node nor
+        link or a name is not well-formed UTF-8, and beyond
+        _lib.DOC_MAX_DEPTH levels.  `atom_docs_stats` counts the calls of
+        each path."""
+        entries, by_id, ids = self._doc_ids(handles_or_ids)
+        if not as_list and len(entries) != 1:
+            raise ValueError("atoms_json: one atom unless as_list")
+        if not by_id and (ids < 0).any():
+            raise ValueError(f"Invalid handle: {entries[int(np.flatnonzero(ids < 0)[0])]}")
+        if self._atom_docs_on_device(entries):
+            ids[(ids < 0) | (ids > _lib.DAS_NONE)] = _lib.DAS_NONE          # no atom has such an id
+            tj, toff = self._type_json_texts()
+            try:
+                got = self.ctx.atoms_json(tj, toff, ids=ids.astype(np.uint32), as_list=as_list)
+            except NotImplementedError:     # no name heap for this index
+                got = None
+            if got is not None and not got[2] and not got[3]:
+                self.atom_docs_stats["device"] += 1
+                return str(got[0].data, "ascii")     # one pass over the bytes: no intermediate copy
+        self.atom_docs_stats["host"] += 1
+        return self.atoms_json_host(entries, as_list)
+
+    def get_atoms_as_dicts_host(self, handles):
+        """get_atoms_as_dicts as the loop over get_atom_as_dict it replaces."""
+        return [self.get_atom_as_dict(h) for h in handles]
+
+    def get_atoms_as_dicts(self, handles):
+        """get_atom_as_dict (redis_mongo_db.py:297-311) of many handles, in
+        input order: {} for a handle the KB does not hold.  Four bulk calls
+        instead of a walk per atom: das_links_outgoing (targets, composite
+        type), das_atoms_info (types), get_node_names and hex_of over all the
+        targets.  A link's `template` comes from a per-load cache keyed by
+        composite-type id, filled by _template_of for the first link of each;
+        every document gets its own copy.  The loop get_atoms_as_dicts_host
+        answers with DAS_ATOM_DOCS=0, below ATOM_DOCS_MIN handles
+        (ATOM_DOCS_MIN_PREFETCHED after prefetch(); ATOM_DOCS_MIN_NODES where
+        all are nodes) and where a link's rows
+        live on another shard.  `atom_docs_stats` counts the calls of each
+        path."""
+        handles = list(handles)
+        if self._atom_docs_on_device(handles):
+            docs = self._dicts_on_device(handles)
+            if docs is not None:
+                self.atom_docs_stats["device"] += 1
+                return docs
+        self.atom_docs_stats["host"] += 1
+        return self.get_atoms_as_dicts_host(handles)
+
+    def _dicts_on_device(self, handles):
+        res = self._resolve(handles)
+        docs = [{} for _ in handles]
+        where = [i for i, (aid, cat, _) in enumerate(res) if aid >= 0 and cat != 0]
+        if not where:
+            return docs
+        ids = np.array([res[i][0] for i in where], dtype=np.uint32)
+        off, tg, ctype, kind = self.ctx.links_outgoing(ids=ids)
+        if (kind == 3).any() or (kind == 0).any():
+            return None
+        ty = self.ctx.atoms_info(ids)[3].tolist()
+        type_names = self.arrays.type_names
+        is_node = kind == 1
+        try:
+            names = iter(self.get_node_names(ids[is_node]) if is_node.any() else ())
+        except NotImplementedError:
+            return None
+        hexes = self.hex_of(tg) if tg.size else []
+        o = off.tolist()
+        cache = self._template_cache
+        for k, i in enumerate(where):
+            h = handles[i]
+            if is_node[k]:
+                docs[i] = {"handle": h, "type": type_names[ty[k]], "name": next(names)}
+                continue
+            ct = int(ctype[k])
+            tpl = cache.get(ct)
+            if tpl is None:
+                tpl = cache[ct] = self._template_of(int(ids[k]))
+            docs[i] = {"handle": h, "type": type_names[ty[k]], "template": _copy_template(tpl),
+                       "targets": hexes[o[k]:o[k + 1]]}
+        return docs
 
     def _type_of(self, aid):
         if self._mirror is not None:

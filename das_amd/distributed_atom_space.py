@@ -138,14 +138,43 @@ class DistributedAtomSpace:
     def count_atoms(self) -> Tuple[int, int]:
         return self.db.count_atoms()
 
+    def _atom_infos(self, handles):
+        """get_atom_as_dict of every handle: one bulk call where the DB has it."""
+        if hasattr(self.db, "get_atoms_as_dicts"):
+            return self.db.get_atoms_as_dicts(handles)
+        return [self.db.get_atom_as_dict(h) for h in handles]
+
+    def _atoms_json(self, handles, as_list=True):
+        """The JSON output of the atoms (the list's dump, or the one atom's):
+        rendered in one call where the DB has it."""
+        if hasattr(self.db, "atoms_json"):
+            return self.db.atoms_json(handles, as_list=as_list)
+        docs = [self.db.get_atom_as_deep_representation(h) for h in handles]
+        return json.dumps(docs if as_list else docs[0], sort_keys=False, indent=4)
+
     def get_atom(self, handle: str, output_format: QueryOutputFormat = QueryOutputFormat.HANDLE):
         if output_format == QueryOutputFormat.HANDLE or not handle:
             atom = self.db.get_atom_as_dict(handle)
             return atom["handle"] if atom else ""
         if output_format == QueryOutputFormat.ATOM_INFO:
-            return self.db.get_atom_as_dict(handle)
+            return self._atom_infos([handle])[0]
         if output_format == QueryOutputFormat.JSON:
-            return json.dumps(self.db.get_atom_as_deep_representation(handle), sort_keys=False, indent=4)
+            return self._atoms_json([handle], as_list=False)
+        raise ValueError(f"Invalid output format: '{output_format}'")
+
+    def get_atoms(self, handles: List[str], output_format: QueryOutputFormat = QueryOutputFormat.HANDLE):
+        """get_atom of many handles as one call: the list of its answers
+        (HANDLE: the handle, "" where the KB does not hold it; ATOM_INFO: the
+        documents, {} likewise and "" for an empty handle); JSON: the dump of
+        the list of deep representations, where a handle the KB does not hold
+        raises ValueError as get_atom does."""
+        handles = list(handles)
+        if output_format == QueryOutputFormat.HANDLE:
+            return [a["handle"] if a else "" for a in self._atom_infos(handles)]
+        if output_format == QueryOutputFormat.ATOM_INFO:
+            return [a if h else "" for h, a in zip(handles, self._atom_infos(handles))]
+        if output_format == QueryOutputFormat.JSON:
+            return self._atoms_json(handles)
         raise ValueError(f"Invalid output format: '{output_format}'")
 
     def get_node(self, node_type: str, node_name: str, output_format: QueryOutputFormat = QueryOutputFormat.HANDLE):
@@ -153,9 +182,9 @@ class DistributedAtomSpace:
         if output_format == QueryOutputFormat.HANDLE or node_handle is None:
             return node_handle
         if output_format == QueryOutputFormat.ATOM_INFO:
-            return self.db.get_atom_as_dict(node_handle)
+            return self._atom_infos([node_handle])[0]
         if output_format == QueryOutputFormat.JSON:
-            return json.dumps(self.db.get_atom_as_deep_representation(node_handle), sort_keys=False, indent=4)
+            return self._atoms_json([node_handle], as_list=False)
         raise ValueError(f"Invalid output format: '{output_format}'")
 
     def get_nodes(self, node_type: str, node_name: str = None, output_format=QueryOutputFormat.HANDLE):
@@ -166,9 +195,9 @@ class DistributedAtomSpace:
         if output_format == QueryOutputFormat.HANDLE or not answer:
             return answer
         if output_format == QueryOutputFormat.ATOM_INFO:
-            return [self.db.get_atom_as_dict(h) for h in answer]
+            return self._atom_infos(answer)
         if output_format == QueryOutputFormat.JSON:
-            return json.dumps([self.db.get_atom_as_deep_representation(h) for h in answer], sort_keys=False, indent=4)
+            return self._atoms_json(answer)
         raise ValueError(f"Invalid output format: '{output_format}'")
 
     def get_link(self, link_type: str, targets: List[str] = None, output_format=QueryOutputFormat.HANDLE):
@@ -176,10 +205,9 @@ class DistributedAtomSpace:
         if link_handle is None or output_format == QueryOutputFormat.HANDLE:
             return link_handle
         if output_format == QueryOutputFormat.ATOM_INFO:
-            return self.db.get_atom_as_dict(link_handle, len(targets))
+            return self._atom_infos([link_handle])[0]
         if output_format == QueryOutputFormat.JSON:
-            return json.dumps(self.db.get_atom_as_deep_representation(link_handle, len(targets)),
-                              sort_keys=False, indent=4)
+            return self._atoms_json([link_handle], as_list=False)
         raise ValueError(f"Invalid output format: '{output_format}'")
 
     def get_links(self, link_type: str, target_types: str = None, targets: List[str] = None,
@@ -204,10 +232,9 @@ class DistributedAtomSpace:
                 return []
             return db_answer if isinstance(db_answer[0], str) else [h for h, _ in db_answer]
         if output_format == QueryOutputFormat.ATOM_INFO:
-            return [self.db.get_atom_as_dict(a if isinstance(a, str) else a[0]) for a in db_answer]
+            return self._atom_infos([a if isinstance(a, str) else a[0] for a in db_answer])
         if output_format == QueryOutputFormat.JSON:
-            return json.dumps([self.db.get_atom_as_deep_representation(a if isinstance(a, str) else a[0])
-                               for a in db_answer], sort_keys=False, indent=4)
+            return self._atoms_json([a if isinstance(a, str) else a[0] for a in db_answer])
         raise ValueError(f"Invalid output format: '{output_format}'")
 
     def get_link_type(self, link_handle: str) -> str:

@@ -260,6 +260,40 @@ int das_node_names(das_ctx_t* ctx, const uint32_t* ids, uint64_t n, const das_ta
                    uint64_t row0, uint64_t* off, uint8_t* bytes, uint64_t cap, uint8_t* kind, uint64_t* n_bytes,
                    uint64_t* n_other);
 
+/* ---- atom documents in bulk (redis_mongo_db.py:187-199, 297-314) ---------- */
+#define DAS_DOC_MAX_DEPTH 16 /* levels of a deep representation (a root is level 1) */
+/* json.dumps(deep representation, sort_keys=False, indent=4) of n atoms as
+ * bytes, rendered on the device.  The roots are given as das_node_names takes
+ * its entries (host `ids`, or rows of a table column), answered in input order,
+ * a repeated root each time.  as_list = 1: the dump of the list of the n
+ * documents ("[]" for n = 0); as_list = 0: the one document alone (n must be
+ * 1).  A node is {"type", "name"}, a link {"type", "targets": [documents]}.
+ * type_json holds each named type's name as JSON text, quotes included, back
+ * to back; type_json_off its n_types + 1 byte offsets (n_types = the index's);
+ * a type of DAS_NONE renders as null.  Names are escaped as ensure_ascii=True
+ * escapes them (das_amd/csrc/json_text.h).
+ * *n_bytes = the total whatever `cap` is; min(total, cap) bytes are copied to
+ * `out` and nothing is stored at or past out[cap] (as das_node_names).
+ * *n_other = visited entries, at any depth, that are neither a node nor a link
+ * (an id >= n_atoms too); *n_bad_utf8 = name bytes that are not well-formed
+ * UTF-8.  If either is non-zero the text is unspecified.  Documents nested
+ * deeper than DAS_DOC_MAX_DEPTH levels return DAS_ERR_LIMIT.  Builds the name
+ * heap if need be (see das_match_node_names). */
+int das_atoms_json(das_ctx_t* ctx, const uint32_t* ids, uint64_t n, const das_table_t* table, int32_t col,
+                   uint64_t row0, uint32_t as_list, const uint8_t* type_json, const uint64_t* type_json_off,
+                   uint32_t n_types, uint8_t* out, uint64_t cap, uint64_t* n_bytes, uint64_t* n_other,
+                   uint64_t* n_bad_utf8);
+/* The outgoing sets of n entries (given as above) in one call: off[i] ..
+ * off[i + 1] are entry i's target ids in `targets`, in stored order (none for
+ * anything that is not a link); *n_targets = the total, min(total, cap) ids are
+ * copied and nothing is stored at or past targets[cap].  ctype[i] = a link's
+ * composite-type id, else DAS_NONE; kind[i] = the category (0 other or an id >=
+ * n_atoms, 1 node, 2 link, 3 link of another shard).  off (n + 1), ctype (n)
+ * and kind (n) are filled in full. */
+int das_links_outgoing(das_ctx_t* ctx, const uint32_t* ids, uint64_t n, const das_table_t* table, int32_t col,
+                       uint64_t row0, uint64_t* off, uint32_t* targets, uint64_t cap, uint64_t* n_targets,
+                       uint32_t* ctype, uint8_t* kind);
+
 /* ---- pattern miner (notebooks/SimplePatternMiner.ipynb cells 6 and 5) ----- */
 #define DAS_HALO_MAX_LEVELS 8
 #define DAS_HALO_BLOCK_ENTRIES 1024 /* incoming-list entries one workgroup marks per pass */
