@@ -115,6 +115,13 @@ void check_schema(int32_t kind, int32_t ncols, const int32_t* vars, const int32_
   }
 }
 
+// The table of a handle with its rows in place: a deferred cross product
+// (Table::prod) is expanded first, once.  Called under the context's lock.
+const Table& settled(das_ctx_t* ctx, const das_table_t* t) {
+  if (t->t.prod) das::resolve_product(ctx->c, const_cast<Table&>(t->t));
+  return t->t;
+}
+
 das_table_t* wrap(std::unique_ptr<Table> t) {
   // das_table holds a Table; take over every field and the device buffer
   auto* w = new das_table;
@@ -536,18 +543,18 @@ int das_node_names(das_ctx_t* ctx, const uint32_t* ids, uint64_t n, const das_ta
     if (table) {
       DAS_CHECK(col >= 0 && col < table->t.ncols, das::DAS_E_INVALID, "bad column");
       DAS_CHECK(row0 <= table->t.nrows && n <= table->t.nrows - row0, das::DAS_E_INVALID, "rows out of range");
-      d_ids = table->t.col(col) + row0;
+      d_ids = settled(ctx, table).col(col) + row0;
     }
     *n_bytes = das::node_names(ctx->c, table ? nullptr : ids, d_ids, n, off, bytes, cap, kind, n_other);
   });
 }
 
 // the ids of a document call: rows [row0, row0 + n) of a table column where they lie, else null (the host ids)
-static const uint32_t* doc_column(const das_table_t* table, int32_t col, uint64_t row0, uint64_t n) {
+static const uint32_t* doc_column(das_ctx_t* ctx, const das_table_t* table, int32_t col, uint64_t row0, uint64_t n) {
   if (!table) return nullptr;
   DAS_CHECK(col >= 0 && col < table->t.ncols, das::DAS_E_INVALID, "bad column");
   DAS_CHECK(row0 <= table->t.nrows && n <= table->t.nrows - row0, das::DAS_E_INVALID, "rows out of range");
-  return table->t.col(col) + row0;
+  return settled(ctx, table).col(col) + row0;
 }
 
 int das_atoms_json(das_ctx_t* ctx, const uint32_t* ids, uint64_t n, const das_table_t* table, int32_t col,
@@ -556,7 +563,7 @@ int das_atoms_json(das_ctx_t* ctx, const uint32_t* ids, uint64_t n, const das_ta
                    uint64_t* n_bad_utf8) {
   return guarded(ctx, [&] {
     DAS_CHECK(n_bytes, das::DAS_E_INVALID, "null argument");
-    const uint32_t* d_ids = doc_column(table, col, row0, n);
+    const uint32_t* d_ids = doc_column(ctx, table, col, row0, n);
     *n_bytes = das::atoms_json(ctx->c, table ? nullptr : ids, d_ids, n, as_list, type_json, type_json_off, n_types,
                                out, cap, n_other, n_bad_utf8);
   });
@@ -567,7 +574,7 @@ int das_links_outgoing(das_ctx_t* ctx, const uint32_t* ids, uint64_t n, const da
                        uint32_t* ctype, uint8_t* kind) {
   return guarded(ctx, [&] {
     DAS_CHECK(n_targets, das::DAS_E_INVALID, "null argument");
-    const uint32_t* d_ids = doc_column(table, col, row0, n);
+    const uint32_t* d_ids = doc_column(ctx, table, col, row0, n);
     *n_targets = das::links_outgoing(ctx->c, table ? nullptr : ids, d_ids, n, off, targets, cap, ctype, kind);
   });
 }
@@ -592,7 +599,7 @@ int das_pattern_counts(das_ctx_t* ctx, const das_table_t* links, const uint32_t*
     if (links) {
       DAS_CHECK(links->t.ncols >= 1 && links->t.kind == DAS_TABLE_ORDERED, das::DAS_E_INVALID,
                 "pattern counts: the links are column 0 of an ordered table");
-      *out = wrap(das::pattern_counts(ctx->c, links->t.col(0), links->t.nrows));
+      *out = wrap(das::pattern_counts(ctx->c, settled(ctx, links).col(0), links->t.nrows));
       return;
     }
     DAS_CHECK(link_ids || !n, das::DAS_E_INVALID, "null argument");
@@ -665,29 +672,29 @@ int das_scan_type(das_ctx_t* ctx, uint32_t type_id, das_table_t** out9) {
 }
 
 int das_join(das_ctx_t* ctx, const das_table_t* a, const das_table_t* b, uint32_t no_overload, das_table_t** out) {
-  return guarded(ctx, [&] { *out = wrap(das::join(ctx->c, a->t, b->t, (int)no_overload)); });
+  return guarded(ctx, [&] { *out = wrap(das::join(ctx->c, settled(ctx, a), settled(ctx, b), (int)no_overload)); });
 }
 
 int das_index_join(das_ctx_t* ctx, const das_table_t* a, const das_link_scan_t* q, das_table_t** out) {
   if (!ctx || !a || !q || !out) return fail(ctx, DAS_ERR_INVALID, "null argument");
   return guarded(ctx, [&] {
-    auto t = das::index_join(ctx->c, a->t, *q);
+    auto t = das::index_join(ctx->c, settled(ctx, a), *q);
     *out = t ? wrap(std::move(t)) : nullptr;
   });
 }
 
 int das_antijoin(das_ctx_t* ctx, const das_table_t* a, const das_table_t* t, das_table_t** out) {
-  return guarded(ctx, [&] { *out = wrap(das::antijoin(ctx->c, a->t, t->t)); });
+  return guarded(ctx, [&] { *out = wrap(das::antijoin(ctx->c, settled(ctx, a), settled(ctx, t))); });
 }
 
 int das_dedup(das_ctx_t* ctx, const das_table_t* a, das_table_t** out) {
-  return guarded(ctx, [&] { *out = wrap(das::dedup(ctx->c, a->t)); });
+  return guarded(ctx, [&] { *out = wrap(das::dedup(ctx->c, settled(ctx, a))); });
 }
 
 int das_concat(das_ctx_t* ctx, const das_table_t* const* ts, uint32_t n, das_table_t** out) {
   return guarded(ctx, [&] {
     std::vector<const Table*> v(n);
-    for (uint32_t i = 0; i < n; ++i) v[i] = &ts[i]->t;
+    for (uint32_t i = 0; i < n; ++i) v[i] = &settled(ctx, ts[i]);
     *out = wrap(das::concat(ctx->c, v.data(), (int)n));
   });
 }
@@ -704,9 +711,15 @@ int das_table_info(const das_table_t* t, int32_t* kind, int32_t* ncols, int32_t*
 int das_table_fetch(das_ctx_t* ctx, const das_table_t* t, uint64_t row0, uint64_t nrows, uint32_t* out) {
   return guarded(ctx, [&] {
     DAS_CHECK(row0 + nrows <= t->t.nrows, das::DAS_E_INVALID, "fetch out of range");
-    for (int c = 0; c < t->t.ncols; ++c)
+    // a deferred cross product: only the rows asked for are expanded, into a
+    // temporary of that size (it stays deferred)
+    std::unique_ptr<Table> part;
+    if (t->t.prod && nrows) part = das::product_rows(ctx->c, t->t, row0, nrows);
+    const Table& src = part ? *part : t->t;
+    const uint64_t r0 = part ? 0 : row0;
+    for (int c = 0; c < src.ncols; ++c)
       if (nrows)
-        DAS_HIP(hipMemcpyAsync(out + (uint64_t)c * nrows, t->t.col(c) + row0, 4 * nrows, hipMemcpyDeviceToHost,
+        DAS_HIP(hipMemcpyAsync(out + (uint64_t)c * nrows, src.col(c) + r0, 4 * nrows, hipMemcpyDeviceToHost,
                                ctx->c.s));
     DAS_HIP(hipStreamSynchronize(ctx->c.s));
   });
@@ -714,6 +727,19 @@ int das_table_fetch(das_ctx_t* ctx, const das_table_t* t, uint64_t row0, uint64_
 
 int das_table_column(const das_table_t* t, int32_t c, uint32_t** dptr) {
   if (!t || c < 0 || c >= t->t.ncols) return fail(nullptr, DAS_ERR_INVALID, "bad column");
+  if (t->t.prod) {
+    // a deferred cross product is expanded with the context that made it
+    Ctx& cx = *t->t.prod->ctx;
+    try {
+      std::lock_guard<std::mutex> lk(cx.mu);
+      ActiveCtx act(&cx);
+      int cur = -1;
+      if (hipGetDevice(&cur) != hipSuccess || cur != cx.device) DAS_HIP(hipSetDevice(cx.device));
+      das::resolve_product(cx, const_cast<Table&>(t->t));
+    } catch (const std::exception& e) {
+      return fail(nullptr, DAS_ERR_INTERNAL, e.what());
+    }
+  }
   *dptr = t->t.col(c);
   return DAS_OK;
 }
@@ -738,7 +764,7 @@ int das_table_free(das_table_t* t) {
 
 int das_partition(das_ctx_t* ctx, const das_table_t* t, const int32_t* key_vars, uint32_t nkey, uint32_t nparts,
                   das_table_t** out, uint64_t* counts) {
-  return guarded(ctx, [&] { *out = wrap(das::partition(ctx->c, t->t, key_vars, nkey, nparts, counts)); });
+  return guarded(ctx, [&] { *out = wrap(das::partition(ctx->c, settled(ctx, t), key_vars, nkey, nparts, counts)); });
 }
 
 int das_table_gather(das_ctx_t* ctx, const das_table_t* t, const uint32_t* idx, uint64_t n, das_table_t** out) {
@@ -750,7 +776,7 @@ int das_table_gather(das_ctx_t* ctx, const das_table_t* t, const uint32_t* idx, 
     }
     das::DBuf<uint32_t> d(n ? n : 1, ctx->c.s);
     if (n) DAS_HIP(hipMemcpyAsync(d.p, idx, 4 * n, hipMemcpyHostToDevice, ctx->c.s));
-    auto g = das::gather_table(ctx->c, t->t, d.p, n);
+    auto g = das::gather_table(ctx->c, settled(ctx, t), d.p, n);
     if (!ascending) g->sorted_col = -1;
     *out = wrap(std::move(g));
     DAS_HIP(hipStreamSynchronize(ctx->c.s));      // `idx` is caller memory
@@ -760,11 +786,11 @@ int das_table_gather(das_ctx_t* ctx, const das_table_t* t, const uint32_t* idx, 
 int das_table_gather_ranges(das_ctx_t* ctx, const das_table_t* t, const uint64_t* begin, const uint64_t* end,
                             uint32_t n_ranges, das_table_t** out) {
   if (!ctx || !t || !out || (n_ranges && (!begin || !end))) return fail(ctx, DAS_ERR_INVALID, "null argument");
-  return guarded(ctx, [&] { *out = wrap(das::gather_ranges(ctx->c, t->t, begin, end, n_ranges)); });
+  return guarded(ctx, [&] { *out = wrap(das::gather_ranges(ctx->c, settled(ctx, t), begin, end, n_ranges)); });
 }
 
 int das_table_export_rows(das_ctx_t* ctx, const das_table_t* t, uint32_t* d_dst) {
-  return guarded(ctx, [&] { das::export_rows(ctx->c, t->t, d_dst); });
+  return guarded(ctx, [&] { das::export_rows(ctx->c, settled(ctx, t), d_dst); });
 }
 
 int das_table_import_rows(das_ctx_t* ctx, int32_t kind, int32_t ncols, const int32_t* vars, const int32_t* member,
@@ -795,7 +821,9 @@ int das_set_pattern_black_list(das_ctx_t* ctx, const uint32_t* type_digests, uin
 int das_table_checksum(das_ctx_t* ctx, const das_table_t* t, const uint64_t* salt, uint64_t out[2]) {
   return guarded(ctx, [&] {
     DAS_CHECK(t && salt && out, das::DAS_E_INVALID, "null argument");
-    das::table_checksum(ctx->c, t->t, salt, out);
+    // a deferred cross product: from its factors' sums (it stays deferred)
+    if (t->t.prod) das::product_checksum(ctx->c, t->t, salt, out);
+    else das::table_checksum(ctx->c, t->t, salt, out);
   });
 }
 
@@ -829,7 +857,7 @@ int das_table_members(const das_table_t* t, int32_t* member) {
 int das_set_dedup(das_ctx_t* ctx, const das_table_t* const* ts, uint32_t n, das_table_t** out) {
   return guarded(ctx, [&] {
     std::vector<const Table*> v(n);
-    for (uint32_t i = 0; i < n; ++i) v[i] = &ts[i]->t;
+    for (uint32_t i = 0; i < n; ++i) v[i] = &settled(ctx, ts[i]);
     auto r = das::set_dedup(ctx->c, v.data(), (int)n);
     for (uint32_t i = 0; i < n; ++i) out[i] = wrap(std::move(r[i]));
   });
@@ -839,8 +867,8 @@ int das_set_minus(das_ctx_t* ctx, const das_table_t* const* a, uint32_t na, cons
                   das_table_t** out) {
   return guarded(ctx, [&] {
     std::vector<const Table*> va(na), vb(nb);
-    for (uint32_t i = 0; i < na; ++i) va[i] = &a[i]->t;
-    for (uint32_t i = 0; i < nb; ++i) vb[i] = &b[i]->t;
+    for (uint32_t i = 0; i < na; ++i) va[i] = &settled(ctx, a[i]);
+    for (uint32_t i = 0; i < nb; ++i) vb[i] = &settled(ctx, b[i]);
     auto r = das::set_minus(ctx->c, va.data(), (int)na, vb.data(), (int)nb);
     for (uint32_t i = 0; i < na; ++i) out[i] = wrap(std::move(r[i]));
   });
@@ -917,7 +945,7 @@ int das_plan_execute_sharded(das_ctx_t* ctx, const das_plan_node_t* nodes, uint3
     return fail(ctx, DAS_ERR_INVALID, "null argument");
   return guarded(ctx, [&] {
     std::vector<const das::Table*> in(n_inputs);
-    for (uint32_t i = 0; i < n_inputs; ++i) in[i] = inputs[i] ? &inputs[i]->t : nullptr;
+    for (uint32_t i = 0; i < n_inputs; ++i) in[i] = inputs[i] ? &settled(ctx, inputs[i]) : nullptr;
     std::vector<uint8_t> ck;
     auto r = das::plan_execute_sharded(ctx->c, nodes, n, (int)no_overload, in, ck);
     *n_out = (uint32_t)r.tables.size();

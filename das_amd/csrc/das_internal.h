@@ -144,6 +144,30 @@ struct Index {
   uint64_t device_bytes = 0;
 };
 
+struct Ctx;
+
+// A cross product kept as its two factors until its rows are read (DESIGN.md
+// §3b): output row o = (probe row o / nb, build row o % nb).  The factors'
+// columns are copies in one allocation of the record's own, never views and
+// never a Rel's.  Shared by the copies of the Table that carries it.
+struct Product {
+  Ctx* ctx = nullptr;               // the context that made it (das_table_column resolves with it)
+  uint32_t* buf = nullptr;          // ncp columns of stride pcap, then ncb columns of stride bcap
+  uint64_t np = 0, nb = 0, pcap = 0, bcap = 0;
+  int ncp = 0, ncb = 0;
+  int32_t pvars[kMaxCols] = {0}, bvars[kMaxCols] = {0};
+  // per output column: side (0 probe, 1 build) and the column of that factor
+  uint8_t side[kMaxCols] = {0}, src[kMaxCols] = {0};
+  const uint32_t* pcol(int k) const { return buf + (uint64_t)k * pcap; }
+  const uint32_t* bcol(int k) const { return buf + (uint64_t)ncp * pcap + (uint64_t)k * bcap; }
+  Product() = default;
+  Product(const Product&) = delete;
+  Product& operator=(const Product&) = delete;
+  ~Product() {
+    if (buf) cache_free(buf);
+  }
+};
+
 struct Table {
   int kind = DAS_TABLE_ORDERED;
   int ncols = 0;
@@ -158,7 +182,13 @@ struct Table {
   uint32_t* data = nullptr;   // ncols columns of `cap` u32 each
   hipStream_t s = nullptr;
   bool view = false;          // data points into an index table (not owned; plan-internal only)
-  uint32_t* col(int c) const { return data + (uint64_t)c * cap; }
+  // set: a cross product not expanded yet (data null, cap 0) -- only the root
+  // And of a plan leaves one, and only the C ABI sees it (resolve_product)
+  std::shared_ptr<Product> prod;
+  uint32_t* col(int c) const {
+    DAS_CHECK(!prod, DAS_E_INTERNAL, "column of an unresolved cross product");
+    return data + (uint64_t)c * cap;
+  }
   ~Table() {
     if (data && !view) cache_free(data);
   }
@@ -448,7 +478,19 @@ void join_ranges(Ctx& c, const ColSet& probe, uint64_t np, const ColSet& build_s
                  uint32_t* cnt);
 std::unique_ptr<Table> scan_link(Ctx& c, const das_link_scan_t& q);
 std::unique_ptr<Table> scan_template(Ctx& c, const das_template_scan_t& q);
-std::unique_ptr<Table> join(Ctx& c, const Table& a, const Table& b, int flags);
+// defer_product: a join without a shared variable (and without no_overload)
+// returns its factors in place of its rows (Table::prod); plan.hip's root And
+// alone asks for it
+std::unique_ptr<Table> join(Ctx& c, const Table& a, const Table& b, int flags, bool defer_product = false);
+// Expands a deferred product in place: its columns allocated on c's stream,
+// the one k_cartesian launch join() would have made, the record dropped.  A
+// table without a record is left as it is.
+void resolve_product(Ctx& c, Table& t);
+// Rows [row0, row0 + n) of a deferred product expanded into a table of n rows
+// (the product itself stays deferred).
+std::unique_ptr<Table> product_rows(Ctx& c, const Table& t, uint64_t row0, uint64_t n);
+// table_checksum of a deferred product from its factors' sums.
+void product_checksum(Ctx& c, const Table& t, const uint64_t* salt, uint64_t out[2]);
 // rows of p whose value of the one shared variable lies in EVERY qs[i]'s key
 // set (each qs[i] one column, distinct keys); nullptr when not applicable
 std::unique_ptr<Table> semi_join_multi(Ctx& c, const Table& p, const std::vector<const Table*>& qs);

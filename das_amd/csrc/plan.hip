@@ -124,12 +124,35 @@ struct Exec {
     return out;
   }
 
-  Rel join_rel(const Rel& a, const Rel& b) {
+  Rel join_rel(const Rel& a, const Rel& b, bool defer = false) {
     Rel out;
     out.partial = a.partial || b.partial;
     for (auto& ta : a.t)
-      for (auto& tb : b.t) out.push(join(c, *ta, *tb, no_overload));
+      for (auto& tb : b.t) out.push(join(c, *ta, *tb, no_overload, defer && defer_rows(ta->nrows, tb->nrows)));
     return out;
+  }
+
+  // Whether the root And's last fold, a cross product of these sizes, stays
+  // its two factors (Table::prod) until its rows are read: above the floor of
+  // a large running result (2^20 rows, as semi_run).  DAS_DEFER_PRODUCT=0
+  // off, =1 without the floor (tests).
+  static bool defer_rows(uint64_t na, uint64_t nb) {
+    const char f = env_char("DAS_DEFER_PRODUCT");
+    if (f == '0') return false;
+    return f == '1' || na * nb > (1ull << 20);
+  }
+
+  // Expands the deferred products among acc's tables that share their schema
+  // with another table of it (normalize would concatenate them).
+  void settle_for_normalize(Rel& acc) {
+    for (size_t i = 0; i < acc.t.size(); ++i) {
+      if (!acc.t[i]->prod) continue;
+      for (size_t j = 0; j < acc.t.size(); ++j)
+        if (j != i && same_schema(*acc.t[i], *acc.t[j])) {
+          resolve_product(c, *acc.t[i]);
+          break;
+        }
+    }
   }
 
   Rel antijoin_rel(Rel r, const Rel& f) {
@@ -292,7 +315,9 @@ struct Exec {
   }
 
   // acc_term: the Link term whose scan alone is acc (-1: acc is anything else)
-  bool step(uint32_t ti, Rel& acc, bool& have, std::vector<Rel>& forbidden, int64_t& acc_term) {
+  // defer: this fold ends the root And (no term, Not filter or antijoin
+  // follows), so a cross product may stay deferred
+  bool step(uint32_t ti, Rel& acc, bool& have, std::vector<Rel>& forbidden, int64_t& acc_term, bool defer = false) {
     const das_plan_node_t& x = nd[ti];
     if (have && x.op == DAS_PLAN_LINK && x.index_join && ne(acc)) {
       // the term's rows looked up from the running result's keys; an empty
@@ -332,7 +357,7 @@ struct Exec {
         acc = Rel{};
         acc.push(std::move(r));
       } else {
-        acc = join_rel(acc, s.rel);
+        acc = join_rel(acc, s.rel, defer);
       }
       acc_term = -1;
     }
@@ -477,9 +502,13 @@ struct Exec {
           continue;
         }
       }
-      if (!step(ti, acc, have, forbidden, acc_term)) return Res{};
+      // the root And's last term with no filter pending: nothing reads the
+      // fold's rows before the plan's answer does
+      const bool last = root && !sharded() && k + 1 == terms.size() && forbidden.empty() && anti.empty();
+      if (!step(ti, acc, have, forbidden, acc_term, last)) return Res{};
       log(1);
     }
+    settle_for_normalize(acc);
     for (auto& f : forbidden)
       if (acc.nonempty()) acc = antijoin_rel(std::move(acc), f);
     for (uint32_t li : anti) {

@@ -425,16 +425,17 @@ __global__ void k_join_expand(const uint64_t* offs, uint64_t np, const uint32_t*
 // division per thread: the grid stride S quads advances (i, j) by
 // (4S / nb, 4S % nb) with a carry.  A pure write stream at ~6 TB/s on MI355X
 // (4-byte stores: ~3.4 TB/s; tools/ubench/cart_bw.hip, profiles/archive/r3_cart_bw.txt).
-// NC: output columns, specialised up to 6.
+// NC: output columns, specialised up to 6.  `total` outputs from product row
+// `first` on (a slice of a deferred product; 0 and np * nb for the whole).
 template <int NC>
-__global__ void __launch_bounds__(B) k_cartesian(OutMap om, uint64_t np, uint64_t nb, uint64_t total, uint64_t sq,
-                                                 uint64_t sr, uint32_t* out, uint64_t cap) {
+__global__ void __launch_bounds__(B) k_cartesian(OutMap om, uint64_t np, uint64_t nb, uint64_t first, uint64_t total,
+                                                 uint64_t sq, uint64_t sr, uint32_t* out, uint64_t cap) {
   typedef uint32_t v4u __attribute__((ext_vector_type(4)));
   const int nc = NC > 0 ? NC : om.n;
   const uint64_t nq = (total + 3) >> 2;
   uint64_t q = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (q >= nq) return;
-  uint64_t i = (q << 2) / nb, j = (q << 2) - i * nb;
+  uint64_t i = (first + (q << 2)) / nb, j = (first + (q << 2)) - i * nb;
   const uint32_t* col[kMaxCols];
   bool side[kMaxCols];
 #pragma unroll
@@ -4944,7 +4945,91 @@ std::unique_ptr<Table> index_join_filtered(Ctx& c, const Table& A, const das_lin
   return finish(std::move(out));
 }
 
-std::unique_ptr<Table> join(Ctx& c, const Table& A, const Table& Bt, int no_overload) {
+namespace {
+// Rows [first, first + n) of the product of np probe and nb build rows (om's
+// columns) into out's rows 0..n: one k_cartesian launch.
+void launch_cartesian(Ctx& c, const OutMap& om, uint64_t np, uint64_t nb, uint64_t first, uint64_t n, Table& out) {
+  const int nu = om.n;
+  ProfScope ps(c, "k_cartesian<" + std::to_string(nu >= 2 && nu <= 6 ? nu : 0) + ">", 4.0 * nu * n);
+  const unsigned cg = grid_for((n + 3) / 4, B);
+  const uint64_t S = 4ull * cg * B, sq = S / nb, sr = S % nb;
+  DAS_CHECK(out.cap % 4 == 0 && out.cap >= ((n + 3) & ~3ull) && (reinterpret_cast<uintptr_t>(out.data) & 15) == 0,
+            DAS_E_INTERNAL, "cartesian: output columns not 16-byte aligned");
+  switch (nu) {
+    case 2: hipLaunchKernelGGL(k_cartesian<2>, dim3(cg), dim3(B), 0, c.s, om, np, nb, first, n, sq, sr, out.data, out.cap); break;
+    case 3: hipLaunchKernelGGL(k_cartesian<3>, dim3(cg), dim3(B), 0, c.s, om, np, nb, first, n, sq, sr, out.data, out.cap); break;
+    case 4: hipLaunchKernelGGL(k_cartesian<4>, dim3(cg), dim3(B), 0, c.s, om, np, nb, first, n, sq, sr, out.data, out.cap); break;
+    case 5: hipLaunchKernelGGL(k_cartesian<5>, dim3(cg), dim3(B), 0, c.s, om, np, nb, first, n, sq, sr, out.data, out.cap); break;
+    case 6: hipLaunchKernelGGL(k_cartesian<6>, dim3(cg), dim3(B), 0, c.s, om, np, nb, first, n, sq, sr, out.data, out.cap); break;
+    default: hipLaunchKernelGGL(k_cartesian<0>, dim3(cg), dim3(B), 0, c.s, om, np, nb, first, n, sq, sr, out.data, out.cap); break;
+  }
+  DAS_HIP(hipGetLastError());
+}
+
+OutMap product_map(const Table& t) {
+  const Product& r = *t.prod;
+  OutMap om{};
+  om.n = t.ncols;
+  for (int k = 0; k < t.ncols; ++k) {
+    om.side[k] = r.side[k];
+    om.col[k] = r.side[k] ? r.bcol(r.src[k]) : r.pcol(r.src[k]);
+  }
+  return om;
+}
+
+// a factor of a deferred product as a table over the record's columns
+Table factor_view(const Table& t, int side) {
+  const Product& r = *t.prod;
+  Table f;
+  f.kind = DAS_TABLE_ORDERED;
+  f.ncols = side ? r.ncb : r.ncp;
+  for (int k = 0; k < f.ncols; ++k) f.vars[k] = side ? r.bvars[k] : r.pvars[k];
+  f.nrows = side ? r.nb : r.np;
+  f.cap = side ? r.bcap : r.pcap;
+  f.data = const_cast<uint32_t*>(side ? r.bcol(0) : r.pcol(0));
+  f.s = t.s;
+  f.view = true;
+  return f;
+}
+}  // namespace
+
+void resolve_product(Ctx& c, Table& t) {
+  if (!t.prod) return;
+  const std::shared_ptr<Product> r = t.prod;            // alive until the launch is made
+  const OutMap om = product_map(t);
+  const uint64_t cap = col_stride(t.nrows ? t.nrows : 1);
+  uint32_t* data = (uint32_t*)cache_alloc(4ull * t.ncols * cap, c.s);
+  t.prod.reset();
+  t.data = data;
+  t.cap = cap;
+  t.s = c.s;
+  launch_cartesian(c, om, r->np, r->nb, 0, t.nrows, t);
+}
+
+std::unique_ptr<Table> product_rows(Ctx& c, const Table& t, uint64_t row0, uint64_t n) {
+  DAS_CHECK(t.prod, DAS_E_INTERNAL, "product_rows: not a deferred product");
+  DAS_CHECK(row0 <= t.nrows && n <= t.nrows - row0, DAS_E_INVALID, "rows out of range");
+  auto out = new_table(c, DAS_TABLE_ORDERED, t.ncols, t.vars, n);
+  out->nrows = n;
+  if (n) launch_cartesian(c, product_map(t), t.prod->np, t.prod->nb, row0, n, *out);
+  return out;
+}
+
+void product_checksum(Ctx& c, const Table& t, const uint64_t* salt, uint64_t out[2]) {
+  DAS_CHECK(t.prod, DAS_E_INTERNAL, "product_checksum: not a deferred product");
+  const Product& r = *t.prod;
+  // a row's value is the product of its columns' values, so the rows' sum is
+  // (sum over P of its columns' product) * (sum over Q of its columns' product)
+  uint64_t sp[kMaxCols] = {0}, sb[kMaxCols] = {0};
+  for (int k = 0; k < t.ncols; ++k) (r.side[k] ? sb : sp)[r.src[k]] = salt[k];
+  uint64_t hp[2], hb[2];
+  table_checksum(c, factor_view(t, 0), sp, hp);
+  table_checksum(c, factor_view(t, 1), sb, hb);
+  out[0] = hp[0] * hb[0];
+  out[1] = hp[1] * r.nb + hb[1] * r.np;
+}
+
+std::unique_ptr<Table> join(Ctx& c, const Table& A, const Table& Bt, int no_overload, bool defer_product) {
   if (A.kind != DAS_TABLE_ORDERED || Bt.kind != DAS_TABLE_ORDERED) return theta_join(c, A, Bt, no_overload);
   // schemas
   std::vector<int32_t> va(A.vars, A.vars + A.ncols), vb(Bt.vars, Bt.vars + Bt.ncols), shared, uni;
@@ -4962,7 +5047,42 @@ std::unique_ptr<Table> join(Ctx& c, const Table& A, const Table& Bt, int no_over
   const Table& P = a_probe ? A : Bt;
   const Table& Q = a_probe ? Bt : A;
   std::unique_ptr<Table> out;
-  if (shared.empty()) {
+  if (shared.empty() && defer_product && !no_overload && P.ncols && Q.ncols) {
+    // the product stays its two factors: their columns copied into one
+    // allocation of the record's own (np + nb rows against np * nb)
+    const uint64_t total = P.nrows * Q.nrows;
+    out = std::make_unique<Table>();           // new_table without the columns
+    out->ncols = nu;
+    for (int k = 0; k < nu; ++k) {
+      out->vars[k] = uni[k];
+      out->member[k] = -1;
+    }
+    out->s = c.s;
+    out->nrows = total;
+    auto r = std::make_shared<Product>();
+    r->ctx = &c;
+    r->np = P.nrows;
+    r->nb = Q.nrows;
+    r->ncp = P.ncols;
+    r->ncb = Q.ncols;
+    r->pcap = col_stride(P.nrows);
+    r->bcap = col_stride(Q.nrows);
+    r->buf = (uint32_t*)cache_alloc(4ull * (r->ncp * r->pcap + r->ncb * r->bcap), c.s);
+    for (int k = 0; k < P.ncols; ++k) {
+      r->pvars[k] = P.vars[k];
+      copy_dev(const_cast<uint32_t*>(r->pcol(k)), P.col(k), 4 * P.nrows, c.s);
+    }
+    for (int k = 0; k < Q.ncols; ++k) {
+      r->bvars[k] = Q.vars[k];
+      copy_dev(const_cast<uint32_t*>(r->bcol(k)), Q.col(k), 4 * Q.nrows, c.s);
+    }
+    for (int k = 0; k < nu; ++k) {
+      const int ip = colof(P, uni[k]);
+      r->side[k] = ip >= 0 ? 0 : 1;
+      r->src[k] = (uint8_t)(ip >= 0 ? ip : colof(Q, uni[k]));
+    }
+    out->prod = std::move(r);
+  } else if (shared.empty()) {
     const uint64_t total = P.nrows * Q.nrows;
     out = new_table(c, DAS_TABLE_ORDERED, nu, uni.data(), total);
     out->nrows = total;
@@ -4973,20 +5093,7 @@ std::unique_ptr<Table> join(Ctx& c, const Table& A, const Table& Bt, int no_over
       if (ip >= 0) { om.col[k] = P.col(ip); om.side[k] = 0; }
       else { om.col[k] = Q.col(colof(Q, uni[k])); om.side[k] = 1; }
     }
-    ProfScope ps(c, "k_cartesian<" + std::to_string(nu >= 2 && nu <= 6 ? nu : 0) + ">", 4.0 * nu * total);
-    const unsigned cg = grid_for((total + 3) / 4, B);
-    const uint64_t S = 4ull * cg * B, sq = S / Q.nrows, sr = S % Q.nrows;
-    DAS_CHECK(out->cap % 4 == 0 && (reinterpret_cast<uintptr_t>(out->data) & 15) == 0, DAS_E_INTERNAL,
-              "cartesian: output columns not 16-byte aligned");
-    switch (nu) {
-      case 2: hipLaunchKernelGGL(k_cartesian<2>, dim3(cg), dim3(B), 0, c.s, om, P.nrows, Q.nrows, total, sq, sr, out->data, out->cap); break;
-      case 3: hipLaunchKernelGGL(k_cartesian<3>, dim3(cg), dim3(B), 0, c.s, om, P.nrows, Q.nrows, total, sq, sr, out->data, out->cap); break;
-      case 4: hipLaunchKernelGGL(k_cartesian<4>, dim3(cg), dim3(B), 0, c.s, om, P.nrows, Q.nrows, total, sq, sr, out->data, out->cap); break;
-      case 5: hipLaunchKernelGGL(k_cartesian<5>, dim3(cg), dim3(B), 0, c.s, om, P.nrows, Q.nrows, total, sq, sr, out->data, out->cap); break;
-      case 6: hipLaunchKernelGGL(k_cartesian<6>, dim3(cg), dim3(B), 0, c.s, om, P.nrows, Q.nrows, total, sq, sr, out->data, out->cap); break;
-      default: hipLaunchKernelGGL(k_cartesian<0>, dim3(cg), dim3(B), 0, c.s, om, P.nrows, Q.nrows, total, sq, sr, out->data, out->cap); break;
-    }
-    DAS_HIP(hipGetLastError());
+    launch_cartesian(c, om, P.nrows, Q.nrows, 0, total, *out);
   } else if (shared.size() == 1 && Q.ncols == 1 && (out = semi_join(c, P, Q))) {
     // key-set filter taken (the build side adds no columns)
   } else if (shared.size() == 1 && (out = direct_join(c, P, Q, shared[0], uni))) {

@@ -455,6 +455,12 @@ int das_set_minus(das_ctx_t* ctx, const das_table_t* const* a, uint32_t na, cons
 
 int das_table_info(const das_table_t* t, int32_t* kind, int32_t* ncols, int32_t* vars,
                    uint64_t* nrows);
+/* A plan's answer table may be a cross product kept as its two factors
+ * (DAS_DEFER_PRODUCT): das_table_info / bounds / members read
+ * host fields, das_table_fetch expands only the rows asked for,
+ * das_table_checksum multiplies the factors' sums, and every other call that
+ * takes the table expands it first, once (das_table_column with the context
+ * that made it).  The rows and their order are those of the written product. */
 /* Copies rows [row0, row0+nrows) column-major into host `out` (ncols*nrows). */
 int das_table_fetch(das_ctx_t* ctx, const das_table_t* t, uint64_t row0, uint64_t nrows,
                     uint32_t* out);
