@@ -78,6 +78,7 @@ class das_name_dfa_t(C.Structure):
 
 
 NAME_STAGE_BYTES = 16384          # DAS_NAME_STAGE_BYTES: name bytes of one tile the matcher stages in LDS
+NAME_FILTER_AUTO, NAME_FILTER_WALK, NAME_FILTER_FLAGS = 0, 1, 2   # DAS_NAME_FILTER_*: das_table_name_filter's mode
 NAME_COPY_WAVE = 64               # DAS_NAME_COPY_WAVE: a longer name is copied by a whole wave
 NAME_FETCH_GUESS = 32             # Context.node_names: bytes per name of the first call's capacity
 DOC_MAX_DEPTH = 16                # DAS_DOC_MAX_DEPTH: levels of a deep representation das_atoms_json renders
@@ -131,6 +132,8 @@ _SIGS = {
     "das_ctype_lookup": (C.c_int, [P, P, P]),
     "das_incoming": (C.c_int, [P, C.c_uint32, P, C.c_uint64, P]),
     "das_match_node_names": (C.c_int, [P, C.c_uint32, P, P, C.c_uint64, P]),
+    "das_scan_node_names": (C.c_int, [P, C.c_uint32, P, C.c_int32, C.POINTER(P)]),
+    "das_table_name_filter": (C.c_int, [P, P, C.c_int32, C.c_uint32, P, C.c_int32, C.POINTER(P)]),
     "das_node_name_stats": (C.c_int, [P, C.c_uint32, P, P, P]),
     "das_node_names": (C.c_int, [P, P, C.c_uint64, P, C.c_int32, C.c_uint64, P, P, C.c_uint64, P, P, P]),
     "das_atoms_json": (C.c_int, [P, P, C.c_uint64, P, C.c_int32, C.c_uint64, C.c_uint32, P, P, C.c_uint32, P,
@@ -599,11 +602,10 @@ class Context:
         check(lib().das_node_name_stats(self.h, int(type_id), C.byref(n), C.byref(b), C.byref(a)), self.h)
         return n.value, b.value, bool(a.value)
 
-    def match_node_names(self, type_id, dfa, cap=None):
-        """Ids (ascending) of the nodes of a named type whose name the DFA
-        accepts (das_match_node_names; `dfa`: name_search.NameDFA or any
-        object with its fields).  cap: copy at most that many ids; the second
-        value is the number of matches."""
+    @staticmethod
+    def _name_dfa(dfa):
+        """(das_name_dfa_t, the arrays it points into) of a name_search.NameDFA
+        or any object with its fields."""
         nxt = np.ascontiguousarray(dfa.next, dtype=np.uint16)
         acc = np.ascontiguousarray(dfa.accept, dtype=np.uint8)
         cls = np.ascontiguousarray(dfa.byte_class, dtype=np.uint8)
@@ -612,6 +614,27 @@ class Context:
         d = das_name_dfa_t(n_states=dfa.n_states, n_classes=dfa.n_classes, start=dfa.start, eot_class=dfa.eot_class,
                            next=ptr(nxt), accept=ptr(acc))
         C.memmove(d.byte_class, cls.tobytes(), 256)
+        return d, (nxt, acc)
+
+    def scan_node_names(self, type_id, dfa, var):
+        """das_scan_node_names: the matches of match_node_names as a device
+        Table of one ordered column binding variable id `var`."""
+        d, keep = self._name_dfa(dfa)
+        return self._table(lib().das_scan_node_names, int(type_id), C.byref(d), int(var))
+
+    def table_name_filter(self, t, var, type_id, dfa, mode=NAME_FILTER_AUTO):
+        """das_table_name_filter: the rows of the ordered Table `t` whose
+        value of variable id `var` is a node of the type with an accepted
+        name (mode: NAME_FILTER_AUTO / _WALK / _FLAGS)."""
+        d, keep = self._name_dfa(dfa)
+        return self._table(lib().das_table_name_filter, t.h, int(var), int(type_id), C.byref(d), int(mode))
+
+    def match_node_names(self, type_id, dfa, cap=None):
+        """Ids (ascending) of the nodes of a named type whose name the DFA
+        accepts (das_match_node_names; `dfa`: name_search.NameDFA or any
+        object with its fields).  cap: copy at most that many ids; the second
+        value is the number of matches."""
+        d, keep = self._name_dfa(dfa)
         if cap is None:
             cap = self.node_name_stats(type_id)[0]
         out = np.empty(max(int(cap), 1), dtype=np.uint32)

@@ -521,6 +521,21 @@ int das_match_node_names(das_ctx_t* ctx, uint32_t type_id, const das_name_dfa_t*
   });
 }
 
+int das_scan_node_names(das_ctx_t* ctx, uint32_t type_id, const das_name_dfa_t* dfa, int32_t var, das_table_t** out) {
+  if (!ctx || !dfa || !out) return fail(ctx, DAS_ERR_INVALID, "null argument");
+  return guarded(ctx, [&] { *out = wrap(das::scan_node_names(ctx->c, type_id, *dfa, var)); });
+}
+
+int das_table_name_filter(das_ctx_t* ctx, const das_table_t* t, int32_t var, uint32_t type_id,
+                          const das_name_dfa_t* dfa, int32_t mode, das_table_t** out) {
+  if (!ctx || !t || !dfa || !out) return fail(ctx, DAS_ERR_INVALID, "null argument");
+  return guarded(ctx, [&] {
+    das::check_name_dfa(*dfa);
+    // (a deferred cross product is expanded first, as for every other operator)
+    *out = wrap(das::table_name_filter(ctx->c, settled(ctx, t), var, type_id, *dfa, mode));
+  });
+}
+
 int das_node_name_stats(das_ctx_t* ctx, uint32_t type_id, uint64_t* n_nodes, uint64_t* n_bytes,
                         uint32_t* ascii_only) {
   return guarded(ctx, [&] {

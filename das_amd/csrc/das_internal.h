@@ -407,6 +407,14 @@ void check_name_dfa(const das_name_dfa_t& d);
 // ids (ascending) of the nodes of `type_id` whose name `d` accepts: the
 // number of matches; min(that, cap) ids copied to the host array out_ids
 uint64_t match_node_names(Ctx& c, uint32_t type_id, const das_name_dfa_t& d, uint32_t* out_ids, uint64_t cap);
+// das_scan_node_names: those ids as a one-column ordered table binding `var`
+// (ascending, sorted_col 0, bounds = the first and last id), left on the device
+std::unique_ptr<struct Table> scan_node_names(Ctx& c, uint32_t type_id, const das_name_dfa_t& d, int32_t var);
+// das_table_name_filter: the rows of the ordered table `t` whose value of
+// `var` is a node of `type_id` whose name `d` accepts, in t's order, with t's
+// schema, bounds and sorted mark (mode: DAS_NAME_FILTER_*)
+std::unique_ptr<struct Table> table_name_filter(Ctx& c, const struct Table& t, int32_t var, uint32_t type_id,
+                                                const das_name_dfa_t& d, int mode);
 // das_node_names: the names of the n ids at d_ids (device) or, d_ids null, at
 // h_ids (host), in input order; off[n + 1], kind[n] and min(total, cap) name
 // bytes copied to the host arrays; returns the total, *n_other = the entries

@@ -19,6 +19,7 @@
 // Fetch (das_node_names): ids -> names, a gather over the same heap; its
 // kernels and their comment stand below the matcher's.
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 
 #include "das_internal.h"
@@ -562,38 +563,145 @@ void check_name_dfa(const das_name_dfa_t& d) {
   }
 }
 
-uint64_t match_node_names(Ctx& c, uint32_t type_id, const das_name_dfa_t& d, uint32_t* out_ids, uint64_t cap) {
+namespace {
+
+// The automaton as the kernels stage it: tab_n entries (the row base of the
+// next state | whether it accepts), then the class of each byte.  `host` is
+// the copy's source: it lives until the stream has been waited on.
+struct StagedDfa {
+  std::vector<uint16_t> host;
+  DBuf<uint16_t> blob;
+  uint32_t tab_n = 0, start = 0, eot = 0;
+  const uint16_t* tab() const { return blob.p; }
+  const uint8_t* cls() const { return reinterpret_cast<const uint8_t*>(blob.p + tab_n); }
+};
+
+void stage_dfa(const das_name_dfa_t& d, hipStream_t s, StagedDfa& a) {
+  const uint32_t nc = d.n_classes;
+  a.tab_n = d.n_states * nc;
+  a.host.assign(a.tab_n + 128, 0);                                // + 256 bytes: the class of each byte
+  for (uint32_t i = 0; i < a.tab_n; ++i) {
+    const uint32_t t = d.next[i];
+    a.host[i] = (uint16_t)(t * nc | (d.accept[t] ? kAcceptBit : 0u));
+  }
+  std::memcpy(a.host.data() + a.tab_n, d.byte_class, 256);
+  a.start = d.start * nc | (d.accept[d.start] ? kAcceptBit : 0u);
+  a.eot = d.eot_class;
+  a.blob.alloc(a.host.size(), s);
+  DAS_HIP(hipMemcpyAsync(a.blob.p, a.host.data(), 2 * a.host.size(), hipMemcpyHostToDevice, s));
+}
+
+// flag[i] = the automaton accepts the name of the i-th node of the type (its
+// nodes are [lo, lo + n) of the node list, n > 0)
+void type_flags(Ctx& c, uint32_t type_id, const StagedDfa& a, uint8_t* flag) {
+  const NameHeap& h = c.idx.names;
+  const uint64_t lo = h.type_lo[type_id], n = h.type_hi[type_id] - lo;
+  const uint64_t tiles = (n + kNameBlock - 1) / kNameBlock;
+  KScope ks("k_name_match", (double)h.type_bytes[type_id] + 8.0 * (n + 1) + (double)n);
+  hipLaunchKernelGGL(k_name_match, dim3(grid_for(tiles, 1, 2048)), dim3(kNameBlock), 0, c.s, (const uint8_t*)h.bytes,
+                     (const uint64_t*)h.off, lo, n, a.tab(), a.tab_n, a.cls(), a.start, a.eot, flag);
+  DAS_HIP(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------
+// Names inside queries (das_table_name_filter): the rows of a binding table
+// whose value in one column is a node of the type with an accepted name.  One
+// lane per row finds its value's slot among the type's nodes (a binary search
+// of that range of the ascending node list: a link, a node of another type,
+// DAS_NONE or an id >= n_atoms is in no slot and indexes nothing) and either
+// walks the name where it lies in the heap (walk) or reads the flag
+// k_name_match left for that slot (flags).  Row flags -> scan -> row indices
+// -> gather_table.
+// ---------------------------------------------------------------------------
+// The slot of `id` in node_id[type_lo, type_hi), or kNoSlot.
+constexpr uint64_t kNoSlot = ~0ull;
+__device__ __forceinline__ uint64_t type_slot(uint32_t id, const uint8_t* __restrict__ cat, uint64_t n_atoms,
+                                              const uint32_t* __restrict__ node_id, uint64_t type_lo,
+                                              uint64_t type_hi) {
+  if (id >= n_atoms || cat[id] != CAT_NODE) return kNoSlot;
+  uint64_t lo = type_lo, hi = type_hi;                            // the first slot of the range whose id is >= id
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if (node_id[mid] < id) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < type_hi && node_id[lo] == id ? lo : kNoSlot;
+}
+
+// walk: flag[i] = ids[i] is a node of the type whose name the automaton
+// accepts, i < n.  The table is staged as k_name_match stages it; the names
+// of a tile's rows are scattered over the heap, so they are walked from it.
+__global__ void __launch_bounds__(kNameBlock) k_name_filter(const uint32_t* __restrict__ ids, uint64_t n,
+                                                           const uint8_t* __restrict__ cat, uint64_t n_atoms,
+                                                           const uint32_t* __restrict__ node_id, uint64_t type_lo,
+                                                           uint64_t type_hi, const uint64_t* __restrict__ hoff,
+                                                           uint64_t n_bytes, const uint8_t* __restrict__ heap,
+                                                           const uint16_t* __restrict__ tab, uint32_t tab_n,
+                                                           const uint8_t* __restrict__ cls, uint32_t start,
+                                                           uint32_t eot, uint8_t* __restrict__ flag) {
+  __shared__ uint16_t s_tab[kMaxTable];
+  __shared__ uint8_t s_cls[256];
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t i = tid; i < tab_n && i < kMaxTable; i += kNameBlock) s_tab[i] = tab[i];
+  s_cls[tid] = cls[tid];
+  __syncthreads();
+  const uint64_t tiles = (n + kNameBlock - 1) / kNameBlock;
+  for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const uint64_t i = t * kNameBlock + tid;
+    if (i >= n) continue;
+    uint32_t st = 0;
+    const uint64_t slot = type_slot(ids[i], cat, n_atoms, node_id, type_lo, type_hi);
+    if (slot != kNoSlot) {
+      const uint64_t o0 = hoff[slot], o1 = hoff[slot + 1];
+      if (o0 <= o1 && o1 <= n_bytes) {                            // the name lies inside the heap
+        st = start;
+        if (!(st & kAcceptBit)) {
+          st = name_walk(HeapWords{reinterpret_cast<const uint32_t*>(heap)}, o0, o1, st, s_tab, s_cls);
+          if (!(st & kAcceptBit)) st = s_tab[st + eot];
+        }
+      }
+    }
+    flag[i] = (uint8_t)(st >> 15);
+  }
+}
+
+// flags: the same, from tflag[slot - type_lo] (k_name_match over the type)
+__global__ void k_name_filter_flags(const uint32_t* __restrict__ ids, uint64_t n, const uint8_t* __restrict__ cat,
+                                    uint64_t n_atoms, const uint32_t* __restrict__ node_id, uint64_t type_lo,
+                                    uint64_t type_hi, const uint8_t* __restrict__ tflag, uint8_t* __restrict__ flag) {
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t slot = type_slot(ids[i], cat, n_atoms, node_id, type_lo, type_hi);
+    flag[i] = slot != kNoSlot ? tflag[slot - type_lo] : (uint8_t)0;
+  }
+}
+
+// idx[pos[i]] = i for every kept row i
+__global__ void k_name_rows(const uint8_t* flag, const uint32_t* pos, uint64_t n, uint32_t* idx) {
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+    if (flag[i]) idx[pos[i]] = (uint32_t)i;
+}
+
+void check_name_query(Ctx& c, uint32_t type_id, const das_name_dfa_t& d) {
   check_name_dfa(d);
   DAS_CHECK(c.idx.built, DAS_E_NOT_BUILT, "index not built");
   DAS_CHECK(type_id < c.idx.n_types, DAS_E_INVALID, "named type id out of range");
+}
+
+}  // namespace
+
+uint64_t match_node_names(Ctx& c, uint32_t type_id, const das_name_dfa_t& d, uint32_t* out_ids, uint64_t cap) {
+  check_name_query(c, type_id, d);
   DAS_CHECK(out_ids || !cap, DAS_E_INVALID, "null id buffer");
   ensure_name_heap(c);
   const NameHeap& h = c.idx.names;
   const uint64_t lo = h.type_lo[type_id], n = h.type_hi[type_id] - lo;
   if (!n) return 0;
   hipStream_t s = c.s;
-  // staged table: the row base of the next state, and whether it accepts
-  const uint32_t nc = d.n_classes, tab_n = d.n_states * nc;
-  std::vector<uint16_t> blob(tab_n + 128);                        // + 256 bytes: the class of each byte
-  for (uint32_t i = 0; i < tab_n; ++i) {
-    const uint32_t t = d.next[i];
-    blob[i] = (uint16_t)(t * nc | (d.accept[t] ? kAcceptBit : 0u));
-  }
-  std::memcpy(blob.data() + tab_n, d.byte_class, 256);
-  const uint32_t start = d.start * nc | (d.accept[d.start] ? kAcceptBit : 0u);
-  DBuf<uint16_t> d_blob(blob.size(), s);
-  DAS_HIP(hipMemcpyAsync(d_blob.p, blob.data(), 2 * blob.size(), hipMemcpyHostToDevice, s));
+  StagedDfa a;
+  stage_dfa(d, s, a);
   DBuf<uint8_t> flag(n, s);
   DBuf<uint32_t> pos(n + 1, s);
-  const uint64_t tiles = (n + kNameBlock - 1) / kNameBlock;
-  const uint64_t range_bytes = h.type_bytes[type_id];
-  {
-    KScope ks("k_name_match", (double)range_bytes + 8.0 * (n + 1) + (double)n);
-    hipLaunchKernelGGL(k_name_match, dim3(grid_for(tiles, 1, 2048)), dim3(kNameBlock), 0, s, (const uint8_t*)h.bytes,
-                       (const uint64_t*)h.off, lo, n, (const uint16_t*)d_blob.p, tab_n,
-                       (const uint8_t*)(d_blob.p + tab_n), start, d.eot_class, flag.p);
-    DAS_HIP(hipGetLastError());
-  }
+  type_flags(c, type_id, a, flag.p);
   uint64_t m = 0;
   {
     KScope ks("name_flag_scan", 2.0 * n + 4.0 * n);
@@ -612,6 +720,119 @@ uint64_t match_node_names(Ctx& c, uint32_t type_id, const das_name_dfa_t& d, uin
     DAS_HIP(hipStreamSynchronize(s));
   }
   return m;
+}
+
+std::unique_ptr<Table> scan_node_names(Ctx& c, uint32_t type_id, const das_name_dfa_t& d, int32_t var) {
+  check_name_query(c, type_id, d);
+  ensure_name_heap(c);
+  const NameHeap& h = c.idx.names;
+  const uint64_t lo = h.type_lo[type_id], n = h.type_hi[type_id] - lo;
+  if (!n) return new_table(c, DAS_TABLE_ORDERED, 1, &var, 0);
+  hipStream_t s = c.s;
+  StagedDfa a;
+  stage_dfa(d, s, a);
+  DBuf<uint8_t> flag(n, s);
+  DBuf<uint32_t> pos(n + 1, s);
+  type_flags(c, type_id, a, flag.p);
+  uint64_t m = 0;
+  {
+    KScope ks("name_flag_scan", 2.0 * n + 4.0 * n);
+    m = scan_total<uint32_t>(ByteFlagIn{flag.p}, n, pos.p, s);     // (waits: the staged table was read)
+  }
+  auto t = new_table(c, DAS_TABLE_ORDERED, 1, &var, m);
+  t->nrows = m;
+  if (!m) return t;
+  {
+    KScope ks("k_name_emit", 5.0 * n + 8.0 * m);
+    hipLaunchKernelGGL(k_name_emit, G(n), dim3(256), 0, s, (const uint8_t*)flag.p, (const uint32_t*)pos.p,
+                       (const uint32_t*)h.node_id + lo, n, t->col(0));
+    DAS_HIP(hipGetLastError());
+  }
+  // the node list ascends: so does the column; its bounds are its ends
+  uint32_t ends[2] = {0, kNone};
+  DAS_HIP(hipMemcpyAsync(&ends[0], t->col(0), 4, hipMemcpyDeviceToHost, s));
+  DAS_HIP(hipMemcpyAsync(&ends[1], t->col(0) + (m - 1), 4, hipMemcpyDeviceToHost, s));
+  DAS_HIP(hipStreamSynchronize(s));
+  t->sorted_col = 0;
+  t->lo[0] = ends[0];
+  t->hi[0] = ends[1];
+  return t;
+}
+
+// das_table_name_filter's automatic mode: flags for a table of at least this
+// many rows per node of the type, walk below.  Measured on 10^7 nodes with
+// 8-byte names (profiles/name_term.json, tools/name_term_bench.py): tables of
+// 10^3 .. 10^8 rows, three patterns; walk is faster up to 10^6 rows (0.27 ms
+// against 0.30 ms there, 0.04 against 0.12 ms at 10^3: flags pays 0.085 ms of
+// k_name_match before it looks at a row) and flags from 10^7 rows on (2.0
+// against 2.3 ms, 18 against 23 ms at 10^8) -- 10^7 rows = 1 row per node, the
+// smallest measured size from which flags was never slower.
+constexpr uint64_t kNameFlagsRowsPerNode = 1;
+
+// DAS_NAME_TERM_FILTER=walk|flags: the mode of every das_table_name_filter
+// call that leaves it open (mode 0); otherwise by kNameFlagsRowsPerNode.
+static int name_filter_mode(int mode, uint64_t rows, uint64_t type_nodes) {
+  if (mode != DAS_NAME_FILTER_AUTO) return mode;
+  const char* e = std::getenv("DAS_NAME_TERM_FILTER");
+  if (e && !std::strcmp(e, "flags")) return DAS_NAME_FILTER_FLAGS;
+  if (e && !std::strcmp(e, "walk")) return DAS_NAME_FILTER_WALK;
+  return rows >= kNameFlagsRowsPerNode * type_nodes ? DAS_NAME_FILTER_FLAGS : DAS_NAME_FILTER_WALK;
+}
+
+std::unique_ptr<Table> table_name_filter(Ctx& c, const Table& t, int32_t var, uint32_t type_id,
+                                         const das_name_dfa_t& d, int mode) {
+  check_name_query(c, type_id, d);
+  DAS_CHECK(mode >= DAS_NAME_FILTER_AUTO && mode <= DAS_NAME_FILTER_FLAGS, DAS_E_INVALID, "name filter: bad mode");
+  DAS_CHECK(t.kind == DAS_TABLE_ORDERED, DAS_E_INVALID, "name filter: the table is not ordered");
+  int col = -1;
+  for (int k = 0; k < t.ncols && col < 0; ++k)
+    if (t.vars[k] == var) col = k;
+  DAS_CHECK(col >= 0, DAS_E_INVALID, "name filter: the table has no column of that variable");
+  ensure_name_heap(c);
+  const NameHeap& h = c.idx.names;
+  const uint64_t n = t.nrows, tlo = h.type_lo[type_id], thi = h.type_hi[type_id], tn = thi - tlo;
+  if (!n || !tn) return gather_table(c, t, nullptr, 0);
+  DAS_CHECK(n < (1ull << 32), DAS_E_UNSUPPORTED, "name filter: too many rows");
+  hipStream_t s = c.s;
+  StagedDfa a;
+  stage_dfa(d, s, a);
+  DBuf<uint8_t> flag(n, s);
+  DBuf<uint32_t> pos(n + 1, s);
+  const uint32_t* ids = t.col(col);
+  const double locate = 4.0 * n + 1.0 * n + 4.0 * n * (double)bits_for(tn);   // value, category, the search
+  DBuf<uint8_t> tflag;
+  if (name_filter_mode(mode, n, tn) == DAS_NAME_FILTER_FLAGS) {
+    tflag.alloc(tn, s);
+    type_flags(c, type_id, a, tflag.p);
+    KScope ks("k_name_filter_flags", locate + 2.0 * n);
+    hipLaunchKernelGGL(k_name_filter_flags, G(n), dim3(256), 0, s, ids, n, (const uint8_t*)c.idx.cat, c.idx.n_atoms,
+                       (const uint32_t*)h.node_id, tlo, thi, (const uint8_t*)tflag.p, flag.p);
+    DAS_HIP(hipGetLastError());
+  } else {
+    // latency-bound, as k_name_copy: a row is a chain of dependent scattered
+    // loads (search, offsets, name words).  Name bytes: the type's mean.
+    const uint64_t tiles = (n + kNameBlock - 1) / kNameBlock;
+    KScope ks("k_name_filter", locate + 16.0 * n + (double)n * ((double)h.type_bytes[type_id] / (double)tn) + 1.0 * n);
+    hipLaunchKernelGGL(k_name_filter, dim3(grid_for(tiles, 1, 2048)), dim3(kNameBlock), 0, s, ids, n,
+                       (const uint8_t*)c.idx.cat, c.idx.n_atoms, (const uint32_t*)h.node_id, tlo, thi,
+                       (const uint64_t*)h.off, h.n_bytes, (const uint8_t*)h.bytes, a.tab(), a.tab_n, a.cls(), a.start,
+                       a.eot, flag.p);
+    DAS_HIP(hipGetLastError());
+  }
+  uint64_t m = 0;
+  {
+    KScope ks("name_row_scan", 2.0 * n + 4.0 * n);
+    m = scan_total<uint32_t>(ByteFlagIn{flag.p}, n, pos.p, s);     // the one read-back (waits: the staged table was read)
+  }
+  if (!m) return gather_table(c, t, nullptr, 0);
+  DBuf<uint32_t> idx(m, s);
+  {
+    KScope ks("k_name_rows", 5.0 * n + 4.0 * m);
+    hipLaunchKernelGGL(k_name_rows, G(n), dim3(256), 0, s, (const uint8_t*)flag.p, (const uint32_t*)pos.p, n, idx.p);
+    DAS_HIP(hipGetLastError());
+  }
+  KScope ks("k_gather_cols", 4.0 * m + 8.0 * t.ncols * m);
+  return gather_table(c, t, idx.p, m);
 }
 
 }  // namespace das

@@ -202,6 +202,7 @@ class HipDB(RelationalDB):
         self.conjunction_stats = {"device": 0, "host": 0}   # conjunction_counts: combinations counted by each path
         self.mine_stats = {"device": 0, "host": 0}          # mine: calls answered by each path
         self.atom_docs_stats = {"device": 0, "host": 0}     # atoms_json / get_atoms_as_dicts: calls of each path
+        self.name_term_stats = {"device": 0, "host": 0}     # NameMatch terms evaluated by each path
         self._type_json = None          # das_atoms_json's type texts, per load
         self._template_cache = {}       # composite-type id -> template of its links, per load
 
@@ -965,11 +966,69 @@ class HipDB(RelationalDB):
                 self.name_search_stats["device"] += 1
                 return self.hex_of(ids) if ids.size else []
         self.name_search_stats["host"] += 1
-        dig, cat, _, ty, nl = self._host_mirror()
+        hits = self._name_hits_host(tid, substring)
+        return _lib.digests_to_hex(self._host_mirror()[0][hits]) if hits else []
+
+    def _name_hits_host(self, tid, pattern):
+        """Ids (ascending) of the nodes of named type `tid` whose name
+        `re.search(pattern, name)` finds: the host loop over the mirror."""
+        _, cat, _, ty, nl = self._host_mirror()
         sel = np.nonzero((cat == 1) & (ty == tid))[0]
-        rx = re.compile(substring)
-        hits = [i for i in sel if rx.search(self.arrays.node_name(int(nl[i])))]
-        return _lib.digests_to_hex(dig[hits]) if hits else []
+        rx = re.compile(pattern)
+        return [i for i in sel if rx.search(self.arrays.node_name(int(nl[i])))]
+
+    # ------------------------------------------------ names inside queries (NameMatch)
+    def _name_term_dfa(self, tid, pattern):
+        """The automaton of a NameMatch term over named type `tid`, or None
+        where the definition path runs: DAS_NAME_TERM=0, a pattern that does
+        not compile to a DFA that is exact for every name of the type
+        (das_amd/name_search.py), an index without a name heap."""
+        if os.environ.get("DAS_NAME_TERM", "1") == "0":
+            return None
+        try:
+            ascii_only = self._name_type_stats(tid)[2]
+        except NotImplementedError:         # no name heap for this index (a type's nodes not one id range)
+            return None
+        return self._name_dfa(pattern, ascii_only)
+
+    def match_node_names_rel(self, node_type, pattern, var_id):
+        """NameMatch.matched: {var: h} for every h of
+        get_matched_node_name(node_type, pattern), as a relation of one
+        ordered one-column table.  Device path: das_scan_node_names, the ids
+        never leave the device.  Definition path (_name_term_dfa): the host
+        `re` loop's ids through table_from_host.  `name_term_stats` counts
+        the terms each path evaluated."""
+        tid = self.type_id.get(node_type)
+        if tid is None:
+            return Relation()
+        dfa = self._name_term_dfa(tid, pattern)
+        if dfa is not None:
+            self.name_term_stats["device"] += 1
+            return Relation([self.ctx.scan_node_names(tid, dfa, var_id)])
+        self.name_term_stats["host"] += 1
+        hits = self._name_hits_host(tid, pattern)
+        if not hits:
+            return Relation()
+        ids = np.asarray(hits, dtype=np.uint32).reshape(1, -1)
+        return Relation([self.ctx.table_from_host(_lib.TABLE_ORDERED, [var_id], ids)])
+
+    def rel_name_filter(self, acc, node_type, pattern, var_id):
+        """And's join of the running relation with a NameMatch term where
+        every table of it is ordered and binds the term's variable: each row
+        covers the term's one-variable assignments, so the join keeps a row
+        iff its value is a match (das_table_name_filter; no scan, no join).
+        None when that does not hold, or on the definition path (the caller
+        evaluates the term and joins)."""
+        if not acc.tables or any(t.kind != _lib.TABLE_ORDERED or var_id not in t.vars for t in acc.tables):
+            return None
+        tid = self.type_id.get(node_type)
+        if tid is None:
+            return None
+        dfa = self._name_term_dfa(tid, pattern)
+        if dfa is None:
+            return None
+        self.name_term_stats["device"] += 1
+        return Relation([self.ctx.table_name_filter(t, var_id, tid, dfa) for t in acc.tables])
 
     def get_atom_as_dict(self, handle, arity=-1) -> dict:
         """redis_mongo_db.py:297-311"""

@@ -21,6 +21,7 @@ compatibility checks, XOR set identity), das_amd/csrc/composite.hip.
 """
 import gc
 import os
+import re
 import struct
 from abc import ABC, abstractmethod
 from collections import Counter
@@ -968,7 +969,8 @@ def _unordered(names, hexcols, cols, i):
 class LogicalExpression(ABC):
     # class tag for the hot lowering / planning walks (isinstance through
     # ABCMeta costs ~0.5 us per call): 'n' Node, 'l' Link, 'v' Variable,
-    # 'tv' TypedVariable, 't' LinkTemplate, 'a' And, 'o' Or, 'x' Not
+    # 'tv' TypedVariable, 't' LinkTemplate, 'a' And, 'o' Or, 'x' Not,
+    # 'm' NameMatch
     _k = ''
 
     @abstractmethod
@@ -1133,6 +1135,54 @@ class LinkTemplate(LogicalExpression):
         return db.rel_nonempty(rel)
 
 
+class NameMatch(LogicalExpression):
+    """A variable constrained by the name of the node it binds (no reference
+    counterpart; the notebooks loop over get_matched_node_name instead).
+
+    Definition: the term's assignments are {OrderedAssignment{variable: h}}
+    for h in db.get_matched_node_name(node_type, pattern) -- re.search of
+    the pattern over the names of the nodes of that type -- and matched() is
+    True iff there is one; an unknown type has none.  Inside And / Or / Not
+    it folds as any term with that assignment set.  The whole-expression
+    plan has no leaf for it: an expression that holds one takes the
+    per-operator fold (_walk raises _Unsupported).
+
+    Evaluation: HipDB.match_node_names_rel (the matcher's ids as a device
+    table), and in And, where the running result already binds the variable
+    in ordered tables, HipDB.rel_name_filter instead of scan + join.
+    DAS_NAME_TERM=0, or a pattern the DFA compiler declines for the type,
+    takes the ids from the host `re` loop; the fold is the same."""
+    _k = 'm'
+
+    def __init__(self, variable_name: str, node_type: str, pattern: str):
+        self.name = variable_name
+        self.node_type = node_type
+        self.pattern = pattern
+        self.regex = re.compile(pattern)        # an invalid pattern raises re.error here
+
+    def __repr__(self):
+        return f'<NameMatch {self.name}: {self.node_type} ~ {self.pattern!r}>'
+
+    @staticmethod
+    def _db(db):
+        db = _hip(db)
+        if not isinstance(db, HipDB):
+            raise NotImplementedError("NameMatch on a sharded DB")
+        return db
+
+    def matched(self, db: DBInterface, answer: PatternMatchingAnswer) -> bool:
+        db = self._db(db)
+        rel = db.match_node_names_rel(self.node_type, self.pattern, _vid(self.name))
+        answer._set(db, rel)
+        return db.rel_nonempty(rel)
+
+    def _filter(self, db, acc):
+        """rel_join(acc, this term's relation) as a filter of acc's rows, or
+        None when acc does not bind the variable in ordered tables only
+        (And.matched evaluates the term and joins instead)."""
+        return self._db(db).rel_name_filter(acc, self.node_type, self.pattern, _vid(self.name))
+
+
 class Not(LogicalExpression):
     _k = 'x'
 
@@ -1234,6 +1284,8 @@ class And(LogicalExpression):
         sorted by its first variable that another term also binds (the join
         key), so joins probe sorted keys.  Answers are unchanged."""
         def names(t):
+            if t._k == 'm':
+                return [t.name]                 # a NameMatch binds its variable: a join key like any other
             return [x.name for x in t.targets if x._k == 'v' or x._k == 'tv'] if t._k == 'l' else []
         vs = [set(names(t)) for t in self.terms]
         for i, t in enumerate(self.terms):
@@ -1264,6 +1316,16 @@ class And(LogicalExpression):
                 # result takes the scan path, which tells a failing term
                 # (And -> False) from an empty join (reset-on-empty)
                 rel = term._index_join(db, acc)
+                if rel is not None and db.rel_nonempty(rel):
+                    acc = rel
+                    continue
+            elif acc is not None and term._k == 'm' and db.rel_nonempty(acc):
+                # name filter (das_table_name_filter): where every row binds
+                # the term's variable the join keeps a row iff its value is
+                # a match; an empty result takes the term's own matched(),
+                # which tells "no name of the type matches" (And -> False)
+                # from an empty join (reset-on-empty)
+                rel = term._filter(db, acc)
                 if rel is not None and db.rel_nonempty(rel):
                     acc = rel
                     continue

@@ -241,6 +241,28 @@ int das_match_node_names(das_ctx_t* ctx, uint32_t type_id, const das_name_dfa_t*
 /* Per named type: its number of nodes, the bytes of their names, and whether
  * every name byte is < 0x80 and not '\n' (builds the name heap if need be). */
 int das_node_name_stats(das_ctx_t* ctx, uint32_t type_id, uint64_t* n_nodes, uint64_t* n_bytes, uint32_t* ascii_only);
+/* The matches of das_match_node_names as a binding table that stays on the
+ * device: one ordered column binding variable `var`, ids ascending and marked
+ * sorted, the column's bounds the first and the last id -- ready to be joined
+ * (das_join, das_index_join).  No match: an empty table, as das_scan_link
+ * returns one.  Errors as das_match_node_names. */
+int das_scan_node_names(das_ctx_t* ctx, uint32_t type_id, const das_name_dfa_t* dfa, int32_t var, das_table_t** out);
+/* The rows of `t` whose value of variable `var` is a node of named type
+ * `type_id` whose name the automaton accepts: every column carried, row order,
+ * schema, bounds and sorted mark kept; a value that repeats is answered each
+ * time; a value that is a link, a node of another type, DAS_NONE or an id >=
+ * n_atoms drops its row.  `t` is ordered and has a column of `var`, else
+ * DAS_ERR_INVALID; a bad DFA is refused before anything is launched.  mode:
+ * WALK -- each row's name is walked where it lies in the heap; FLAGS -- the
+ * whole type is matched once (as das_match_node_names) and a row reads its
+ * node's flag; AUTO -- the library's choice, or what the environment variable
+ * DAS_NAME_TERM_FILTER=walk|flags says.  One read-back (the kept count); no
+ * resident memory beyond the name heap, built if need be. */
+#define DAS_NAME_FILTER_AUTO 0
+#define DAS_NAME_FILTER_WALK 1
+#define DAS_NAME_FILTER_FLAGS 2
+int das_table_name_filter(das_ctx_t* ctx, const das_table_t* t, int32_t var, uint32_t type_id,
+                          const das_name_dfa_t* dfa, int32_t mode, das_table_t** out);
 
 /* ---- node-name fetch (get_node_name in bulk, redis_mongo_db.py:281-285) ---- */
 #define DAS_NAME_COPY_WAVE 64 /* a name longer than this many bytes is copied by a whole wave */
