@@ -21,6 +21,10 @@ struct das_ctx {
 };
 struct das_table {
   Table t;
+  // the record Ctx::aliases listed for this handle (wrap), kept to the end
+  // so that das_table_free finds the context without reading t.lazy, which
+  // a rebuild on another thread may be dropping
+  std::shared_ptr<das::Lazy> reg;
 };
 struct das_parsed {
   std::unique_ptr<das::Parsed> p;
@@ -115,18 +119,28 @@ void check_schema(int32_t kind, int32_t ncols, const int32_t* vars, const int32_
   }
 }
 
-// The table of a handle with its rows in place: a deferred cross product
-// (Table::prod) is expanded first, once.  Called under the context's lock.
+// The table of a handle with its rows in place: an unresolved answer
+// (Table::lazy) is settled first, once.  Called under the context's lock.
 const Table& settled(das_ctx_t* ctx, const das_table_t* t) {
-  if (t->t.prod) das::resolve_product(ctx->c, const_cast<Table&>(t->t));
+  if (t->t.lazy) {
+    DAS_CHECK(!t->t.lazy->aliases_index() || t->t.lazy->ctx == &ctx->c, das::DAS_E_INVALID,
+              "an unresolved answer is read through the context that made it");
+    das::settle(ctx->c, const_cast<Table&>(t->t));
+  }
   return t->t;
 }
 
+// Called under the context's lock: an answer that reads index arrays is
+// listed in the context's alias registry from here on.
 das_table_t* wrap(std::unique_ptr<Table> t) {
   // das_table holds a Table; take over every field and the device buffer
   auto* w = new das_table;
   w->t = *t;
   t->data = nullptr;
+  if (w->t.lazy && w->t.lazy->aliases_index()) {
+    das::register_alias(w->t);
+    w->reg = w->t.lazy;
+  }
   return w;
 }
 
@@ -196,7 +210,7 @@ int das_ctx_destroy(das_ctx_t* ctx) {
     das::prof_collect(ctx->c);
     for (hipEvent_t e : ctx->c.ev_pool) (void)hipEventDestroy(e);
     ctx->c.ev_pool.clear();
-    das::free_index(ctx->c.idx);
+    das::free_index(ctx->c);
     ctx->c.zlc.release();                 // back to the cache while the stream still exists
     das::cache_release_stream(ctx->c.s);
     for (auto& z : ctx->c.zlc_side) z.release();
@@ -657,7 +671,20 @@ int das_ctype_lookup(das_ctx_t* ctx, const uint32_t digest[4], int64_t* ctype_id
 }
 
 int das_scan_link(das_ctx_t* ctx, const das_link_scan_t* q, das_table_t** out) {
-  return guarded(ctx, [&] { *out = wrap(das::scan_link(ctx->c, *q)); });
+  return guarded(ctx, [&] {
+    // a large scan that is a range of index columns stays a view of them
+    // (Lazy::VIEW) until its rows are read: no copy for a caller that only
+    // counts it.  scan_estimate bounds the output, so smaller scans take the
+    // path they always took.
+    struct Views {
+      Ctx& c;
+      ~Views() { c.scan_views = 0; }
+    } v{ctx->c};
+    if (q->ordered && das::defer_join_rows(0, das::scan_estimate(ctx->c, *q))) ctx->c.scan_views = 1;
+    auto t = das::scan_link(ctx->c, *q);
+    if (t->view) das::make_lazy_view(ctx->c, *t);
+    *out = wrap(std::move(t));
+  });
 }
 
 int das_scan_template(das_ctx_t* ctx, const das_template_scan_t* q, das_table_t** out) {
@@ -727,30 +754,33 @@ int das_table_fetch(das_ctx_t* ctx, const das_table_t* t, uint64_t row0, uint64_
   return guarded(ctx, [&] {
     DAS_CHECK(row0 + nrows <= t->t.nrows, das::DAS_E_INVALID, "fetch out of range");
     // a deferred cross product: only the rows asked for are expanded, into a
-    // temporary of that size (it stays deferred)
+    // temporary of that size (it stays deferred); a view is read in place;
+    // a deferred expansion is settled
     std::unique_ptr<Table> part;
-    if (t->t.prod && nrows) part = das::product_rows(ctx->c, t->t, row0, nrows);
+    const das::Lazy* lz = t->t.lazy.get();
+    if (lz && lz->kind == das::Lazy::PRODUCT && nrows) part = das::product_rows(ctx->c, t->t, row0, nrows);
+    else if (lz && lz->kind == das::Lazy::EXPAND) settled(ctx, t);
     const Table& src = part ? *part : t->t;
     const uint64_t r0 = part ? 0 : row0;
     for (int c = 0; c < src.ncols; ++c)
       if (nrows)
-        DAS_HIP(hipMemcpyAsync(out + (uint64_t)c * nrows, src.col(c) + r0, 4 * nrows, hipMemcpyDeviceToHost,
-                               ctx->c.s));
+        DAS_HIP(hipMemcpyAsync(out + (uint64_t)c * nrows, src.data + (uint64_t)c * src.cap + r0, 4 * nrows,
+                               hipMemcpyDeviceToHost, ctx->c.s));
     DAS_HIP(hipStreamSynchronize(ctx->c.s));
   });
 }
 
 int das_table_column(const das_table_t* t, int32_t c, uint32_t** dptr) {
   if (!t || c < 0 || c >= t->t.ncols) return fail(nullptr, DAS_ERR_INVALID, "bad column");
-  if (t->t.prod) {
-    // a deferred cross product is expanded with the context that made it
-    Ctx& cx = *t->t.prod->ctx;
+  if (t->t.lazy) {
+    // an unresolved answer is settled with the context that made it
+    Ctx& cx = *t->t.lazy->ctx;
     try {
       std::lock_guard<std::mutex> lk(cx.mu);
       ActiveCtx act(&cx);
       int cur = -1;
       if (hipGetDevice(&cur) != hipSuccess || cur != cx.device) DAS_HIP(hipSetDevice(cx.device));
-      das::resolve_product(cx, const_cast<Table&>(t->t));
+      das::settle(cx, const_cast<Table&>(t->t));
     } catch (const std::exception& e) {
       return fail(nullptr, DAS_ERR_INTERNAL, e.what());
     }
@@ -773,6 +803,16 @@ int das_table_from_host(das_ctx_t* ctx, int32_t kind, int32_t ncols, const int32
 }
 
 int das_table_free(das_table_t* t) {
+  if (t && t->reg && t->reg->listed.load(std::memory_order_acquire)) {
+    // off the alias registry first, under the lock a rebuild settles it under
+    // (a settled record is off it already, and its context may be gone); the
+    // record alone is then freed
+    Ctx& cx = *t->reg->ctx;
+    std::lock_guard<std::mutex> lk(cx.mu);
+    das::deregister_alias(*t->reg);
+    delete t;
+    return DAS_OK;
+  }
   delete t;
   return DAS_OK;
 }
@@ -836,9 +876,10 @@ int das_set_pattern_black_list(das_ctx_t* ctx, const uint32_t* type_digests, uin
 int das_table_checksum(das_ctx_t* ctx, const das_table_t* t, const uint64_t* salt, uint64_t out[2]) {
   return guarded(ctx, [&] {
     DAS_CHECK(t && salt && out, das::DAS_E_INVALID, "null argument");
-    // a deferred cross product: from its factors' sums (it stays deferred)
-    if (t->t.prod) das::product_checksum(ctx->c, t->t, salt, out);
-    else das::table_checksum(ctx->c, t->t, salt, out);
+    // a deferred cross product: from its factors' sums (it stays deferred);
+    // a view or a deferred expansion is settled
+    if (t->t.lazy && t->t.lazy->kind == das::Lazy::PRODUCT) das::product_checksum(ctx->c, t->t, salt, out);
+    else das::table_checksum(ctx->c, settled(ctx, t), salt, out);
   });
 }
 

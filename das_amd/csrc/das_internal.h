@@ -2,6 +2,7 @@
 // device binding tables.  Layout rationale is in DESIGN.md §3.
 #pragma once
 #include <array>
+#include <atomic>
 #include <map>
 #include <unordered_map>
 #include <memory>
@@ -145,13 +146,41 @@ struct Index {
 };
 
 struct Ctx;
+struct Table;
 
-// A cross product kept as its two factors until its rows are read (DESIGN.md
-// §3b): output row o = (probe row o / nb, build row o % nb).  The factors'
-// columns are copies in one allocation of the record's own, never views and
-// never a Rel's.  Shared by the copies of the Table that carries it.
-struct Product {
-  Ctx* ctx = nullptr;               // the context that made it (das_table_column resolves with it)
+// What a deferred index-join expansion keeps (query.hip): the arguments of
+// the dj_write launch index_join would have made.
+struct Expansion;
+struct ExpansionDel {
+  void operator()(Expansion* e) const;
+};
+
+// The rows of a plan's answer that nothing has read yet.
+// Shared by the copies of the Table that carries it.  Kinds:
+//   PRODUCT  a cross product kept as its two factors: output row o = (probe
+//            row o / nb, build row o % nb).  The factors' columns are copies
+//            in one allocation of the record's own, never views and never a
+//            Rel's.
+//   VIEW     a scan that is a range of consecutive index columns: the table's
+//            data / cap point at them (Table::view), settling copies them.
+//   EXPAND   an index join stopped after its count pass: `exp` holds the
+//            probe rows, the (first, count) of each and the unit offsets;
+//            settling allocates the columns and makes the one dj_write launch.
+// A VIEW or EXPAND record reads index arrays, so the handle that carries one
+// is listed in its context's alias registry (Ctx::aliases) until it is
+// settled or freed: whatever releases or replaces index arrays settles every
+// listed table first (settle_aliases).
+struct Lazy {
+  enum Kind : uint8_t { PRODUCT = 0, VIEW = 1, EXPAND = 2 };
+  Kind kind = PRODUCT;
+  Ctx* ctx = nullptr;               // the context that made it (das_table_column settles with it)
+  Table* owner = nullptr;           // VIEW / EXPAND: the handle's table while Ctx::aliases lists the record
+  // owner != nullptr, readable without the context's lock: das_table_free
+  // takes the lock (and so needs the context alive) only while this is set
+  std::atomic<bool> listed{false};
+  std::unique_ptr<Expansion, ExpansionDel> exp;   // EXPAND
+  bool aliases_index() const { return kind != PRODUCT; }
+  // PRODUCT
   uint32_t* buf = nullptr;          // ncp columns of stride pcap, then ncb columns of stride bcap
   uint64_t np = 0, nb = 0, pcap = 0, bcap = 0;
   int ncp = 0, ncb = 0;
@@ -160,10 +189,10 @@ struct Product {
   uint8_t side[kMaxCols] = {0}, src[kMaxCols] = {0};
   const uint32_t* pcol(int k) const { return buf + (uint64_t)k * pcap; }
   const uint32_t* bcol(int k) const { return buf + (uint64_t)ncp * pcap + (uint64_t)k * bcap; }
-  Product() = default;
-  Product(const Product&) = delete;
-  Product& operator=(const Product&) = delete;
-  ~Product() {
+  Lazy() = default;
+  Lazy(const Lazy&) = delete;
+  Lazy& operator=(const Lazy&) = delete;
+  ~Lazy() {
     if (buf) cache_free(buf);
   }
 };
@@ -181,12 +210,13 @@ struct Table {
   uint64_t nrows = 0, cap = 0;
   uint32_t* data = nullptr;   // ncols columns of `cap` u32 each
   hipStream_t s = nullptr;
-  bool view = false;          // data points into an index table (not owned; plan-internal only)
-  // set: a cross product not expanded yet (data null, cap 0) -- only the root
-  // And of a plan leaves one, and only the C ABI sees it (resolve_product)
-  std::shared_ptr<Product> prod;
+  bool view = false;          // data points into an index table (not owned; plan-internal, or a Lazy::VIEW answer)
+  // set: rows not written yet (PRODUCT / EXPAND: data null, cap 0; VIEW: data
+  // in the index) -- only a plan's answer carries one, and only the C ABI
+  // sees it (settle)
+  std::shared_ptr<Lazy> lazy;
   uint32_t* col(int c) const {
-    DAS_CHECK(!prod, DAS_E_INTERNAL, "column of an unresolved cross product");
+    DAS_CHECK(!lazy, DAS_E_INTERNAL, "column of an unresolved table");
     return data + (uint64_t)c * cap;
   }
   ~Table() {
@@ -256,6 +286,10 @@ struct Ctx {
   bool own_stream = false;
   std::string err;
   std::mutex mu;
+  // alias registry: the Lazy::VIEW / EXPAND records of live answer handles,
+  // which read idx's arrays.  Read and written under `mu` only; emptied by
+  // settle_aliases before index arrays are released.
+  std::vector<Lazy*> aliases;
   Index idx;
   HostScalar scratch;
   // (lo, cnt) descriptor array of the sparse direct-join build, all-zero
@@ -392,7 +426,8 @@ void numbered_strings(const char* prefix, uint64_t plen, uint64_t first, uint64_
 void synth_powerlaw_links(uint32_t* d_child, uint64_t first, uint64_t n, uint32_t K, uint32_t n_link_types,
                           uint32_t type_leaf0, uint32_t node_leaf0, uint64_t n_nodes, double s, uint64_t seed,
                           hipStream_t st);
-void free_index(Index& idx);
+// Releases the index arrays; the tables Ctx::aliases lists are settled first.
+void free_index(Ctx& c);
 void lookup_digests(Ctx& c, const Digest* h_digests, uint64_t n, int64_t* h_ids);
 // ids + category / arity / type of up to 4096 handles in one pinned round
 // trip (false: batch too large, use lookup_digests + das_atoms_info)
@@ -487,13 +522,28 @@ void join_ranges(Ctx& c, const ColSet& probe, uint64_t np, const ColSet& build_s
 std::unique_ptr<Table> scan_link(Ctx& c, const das_link_scan_t& q);
 std::unique_ptr<Table> scan_template(Ctx& c, const das_template_scan_t& q);
 // defer_product: a join without a shared variable (and without no_overload)
-// returns its factors in place of its rows (Table::prod); plan.hip's root And
+// returns its factors in place of its rows (Table::lazy); plan.hip's root And
 // alone asks for it
 std::unique_ptr<Table> join(Ctx& c, const Table& a, const Table& b, int flags, bool defer_product = false);
-// Expands a deferred product in place: its columns allocated on c's stream,
-// the one k_cartesian launch join() would have made, the record dropped.  A
-// table without a record is left as it is.
-void resolve_product(Ctx& c, Table& t);
+// Gives an unresolved table rows of its own, in place, on c's stream: the
+// one k_cartesian launch join() would have made (PRODUCT), the one dj_write
+// launch index_join would have made (EXPAND), a copy of the index columns
+// (VIEW).  The record is dropped and, where the registry lists it, taken off
+// (under the context's lock).  A table without a record is left as it is.
+void settle(Ctx& c, Table& t);
+// Lists the VIEW / EXPAND record of a handle's table in its context's
+// registry (the C ABI, when a plan's answer gets its handle), and takes the
+// record of a handle about to be freed off it.  Under the context's lock.
+void register_alias(Table& t);
+void deregister_alias(Lazy& r);
+// Settles every table the registry lists (before index arrays are released).
+void settle_aliases(Ctx& c);
+// Whether an index join / a scan of these sizes that ends a plan may stay
+// deferred: DAS_DEFER_JOIN=0 never, =1 always (tests), unset: an output above
+// 2^20 rows whose probe side is at most a quarter of it.
+bool defer_join_rows(uint64_t probe_rows, uint64_t out_rows);
+// A view of index columns that is a plan's answer, as an unresolved table.
+void make_lazy_view(Ctx& c, Table& t);
 // Rows [row0, row0 + n) of a deferred product expanded into a table of n rows
 // (the product itself stays deferred).
 std::unique_ptr<Table> product_rows(Ctx& c, const Table& t, uint64_t row0, uint64_t n);
@@ -506,7 +556,13 @@ std::unique_ptr<Table> semi_join_multi(Ctx& c, const Table& p, const std::vector
 // every qs[i]'s key set, filtered during the expansion; nullptr: not applicable
 std::unique_ptr<Table> index_join_filtered(Ctx& c, const Table& a, const das_link_scan_t& q, int32_t fvar,
                                            const std::vector<const Table*>& qs);
-std::unique_ptr<Table> index_join(Ctx& c, const Table& a, const das_link_scan_t& q);   // nullptr: not applicable
+// nullptr: not applicable.  take: plan.hip's root And alone passes it, when
+// nothing reads the join's rows before the plan's answer does -- `a` is then
+// *take, and where the join goes through its count pass (k_ij_lc) and
+// defer_join_rows allows, the output comes back unresolved (Lazy::EXPAND)
+// with *take moved into its record.
+std::unique_ptr<Table> index_join(Ctx& c, const Table& a, const das_link_scan_t& q,
+                                  std::unique_ptr<Table>* take = nullptr);
 // rows of a whose link (q's grounded targets + a's values of q's variables)
 // does not exist; nullptr when a does not bind every variable position
 std::unique_ptr<Table> anti_index_join(Ctx& c, const Table& a, const das_link_scan_t& q);

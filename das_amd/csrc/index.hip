@@ -1338,7 +1338,10 @@ __global__ void k_bdir_fill(const uint64_t* ukey, uint64_t klo, uint64_t n, uint
 }
 }  // namespace
 
-void free_index(Index& idx) {
+void free_index(Ctx& c) {
+  // answers that still read the index arrays get rows of their own first
+  settle_aliases(c);
+  Index& idx = c.idx;
   for (void* p : idx.owned) cache_free(p);
   idx.owned.clear();
   idx = Index();
@@ -1572,7 +1575,7 @@ void build_index(Ctx& c, const das_atoms_t& a, uint32_t flags, uint32_t shard_ra
   // expr_ctype_leaf are device pointers (resident input, nothing uploaded)
   const bool dev_expr = (flags & DAS_BUILD_EXPR_ON_DEVICE) != 0;
   hipStream_t s = c.s;
-  free_index(c.idx);
+  free_index(c);
   Index& idx = c.idx;
   idx.stream = s;
   idx.shard_world = shard_world;

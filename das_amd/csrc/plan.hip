@@ -133,7 +133,7 @@ struct Exec {
   }
 
   // Whether the root And's last fold, a cross product of these sizes, stays
-  // its two factors (Table::prod) until its rows are read: above the floor of
+  // its two factors (Table::lazy) until its rows are read: above the floor of
   // a large running result (2^20 rows, as semi_run).  DAS_DEFER_PRODUCT=0
   // off, =1 without the floor (tests).
   static bool defer_rows(uint64_t na, uint64_t nb) {
@@ -142,14 +142,14 @@ struct Exec {
     return f == '1' || na * nb > (1ull << 20);
   }
 
-  // Expands the deferred products among acc's tables that share their schema
-  // with another table of it (normalize would concatenate them).
+  // Settles the unresolved tables among acc's that share their schema with
+  // another table of it (normalize would concatenate them).
   void settle_for_normalize(Rel& acc) {
     for (size_t i = 0; i < acc.t.size(); ++i) {
-      if (!acc.t[i]->prod) continue;
+      if (!acc.t[i]->lazy) continue;
       for (size_t j = 0; j < acc.t.size(); ++j)
         if (j != i && same_schema(*acc.t[i], *acc.t[j])) {
-          resolve_product(c, *acc.t[i]);
+          settle(c, *acc.t[i]);
           break;
         }
     }
@@ -302,7 +302,9 @@ struct Exec {
   // from a contiguous P row.  Same rows as the join (a two-term join is
   // symmetric, and an empty join empties acc either way), other row order.
   // DAS_REV_IJ=0 off, =1 without the 2^16-row floor (tests).
-  TablePtr reverse_ij(int64_t t0, const Rel& acc, const Rel& s) {
+  // defer: the fold ends the root And -- the expansion may stay deferred
+  // (index_join's `take`: s's table then moves into the answer's record)
+  TablePtr reverse_ij(int64_t t0, const Rel& acc, Rel& s, bool defer) {
     const char f = env_char("DAS_REV_IJ");
     if (t0 < 0 || sharded() || f == '0') return nullptr;
     const das_plan_node_t& a = nd[t0];
@@ -311,12 +313,13 @@ struct Exec {
     const Table& small = *s.t[0];
     if (small.kind != DAS_TABLE_ORDERED || !small.nrows || 4 * small.nrows > big.nrows) return nullptr;
     if (f != '1' && big.nrows < (1ull << 16)) return nullptr;
-    return index_join(c, small, a.ij);
+    return index_join(c, small, a.ij, defer && !no_overload ? &s.t[0] : nullptr);
   }
 
   // acc_term: the Link term whose scan alone is acc (-1: acc is anything else)
   // defer: this fold ends the root And (no term, Not filter or antijoin
-  // follows), so a cross product may stay deferred
+  // follows), so a cross product or an index join's expansion may stay
+  // deferred
   bool step(uint32_t ti, Rel& acc, bool& have, std::vector<Rel>& forbidden, int64_t& acc_term, bool defer = false) {
     const das_plan_node_t& x = nd[ti];
     if (have && x.op == DAS_PLAN_LINK && x.index_join && ne(acc)) {
@@ -327,7 +330,8 @@ struct Exec {
       r.partial = sharded();              // looked up in this shard's index
       bool ok = true;
       for (auto& t : acc.t) {
-        auto j = index_join(c, *t, x.ij);
+        // (deferred: t moves into the record of j, which is not empty)
+        auto j = index_join(c, *t, x.ij, defer && !no_overload && acc.t.size() == 1 ? &t : nullptr);
         if (!j) {
           ok = false;
           break;
@@ -352,7 +356,7 @@ struct Exec {
       have = true;
       acc_term = x.op == DAS_PLAN_LINK ? (int64_t)ti : -1;
     } else {
-      TablePtr r = reverse_ij(acc_term, acc, s.rel);
+      TablePtr r = reverse_ij(acc_term, acc, s.rel, defer);
       if (r) {
         acc = Rel{};
         acc.push(std::move(r));
@@ -611,13 +615,17 @@ uint64_t shape_hash(const das_plan_node_t* nd, uint32_t n) {
   return h;
 }
 
-// a plan's answer: a view must not outlive the index, so the caller gets a copy
+// a plan's answer: a view must not outlive the index, so the caller gets a
+// copy -- made now, or (a large view, defer_join_rows) when its rows are read
+// or the index goes, whichever is first (Lazy::VIEW)
 PlanOutput output(Ctx& c, Res r) {
   PlanOutput out;
   out.matched = r.matched;
   out.negation = r.neg;
   for (auto& t : r.rel.t) {
-    if (t->view) {
+    if (t->view && !t->lazy && defer_join_rows(0, t->nrows)) {
+      make_lazy_view(c, *t);
+    } else if (t->view) {
       auto m = new_table_like(c, *t, t->nrows);
       m->nrows = t->nrows;
       for (int k = 0; k < t->ncols; ++k) copy_dev(m->col(k), t->col(k), 4 * t->nrows, c.s);

@@ -2432,12 +2432,22 @@ std::unique_ptr<Table> scan_template(Ctx& c, const das_template_scan_t& q) {
 // binary search).
 // Probe expansion shared by the direct-address join and the index join:
 // probe row r matches the build rows lc[pkey[r] - kmin] = (first, count).
-std::unique_ptr<Table> dj_expand(Ctx& c, const Table& P, const uint32_t* pkey, uint32_t kmin, uint64_t range,
-                                 const uint2* lc, const JoinCols& jc, int nu, const int32_t* uni,
-                                 double build_bytes) {
-  const uint64_t units = (P.nrows + kXRows - 1) / kXRows;
-  const unsigned grid = grid_for(units, B / 64, 65535u * 4u);
-  DBuf<uint64_t> tot(units, c.s), toff(units + 1, c.s);
+// The expansion's count pass: what its write pass is launched with.
+struct DjCount {
+  uint64_t units = 0, total = 0;
+  unsigned grid = 0;
+  bool balanced = false;
+  DBuf<uint64_t> toff;               // units + 1 output offsets (toff[units] = total)
+};
+
+DjCount dj_count(Ctx& c, const Table& P, const uint32_t* pkey, uint32_t kmin, uint64_t range, const uint2* lc,
+                 const JoinCols& jc) {
+  DjCount k;
+  const uint64_t units = k.units = (P.nrows + kXRows - 1) / kXRows;
+  const unsigned grid = k.grid = grid_for(units, B / 64, 65535u * 4u);
+  DBuf<uint64_t> tot(units, c.s);
+  DBuf<uint64_t>& toff = k.toff;
+  toff.alloc(units + 1, c.s);
   bool fused = false;
   PubSlot ps_count{};
   {
@@ -2473,7 +2483,7 @@ std::unique_ptr<Table> dj_expand(Ctx& c, const Table& P, const uint32_t* pkey, u
   } else {
     tm[0] = scan_total<uint64_t>(SpanIn<uint64_t>{tot.p}, units, toff.p, c.s, &tm[1]);   // toff[units] = total
   }
-  const uint64_t total = tm[0];
+  const uint64_t total = k.total = tm[0];
   // a unit owning far more outputs than a wave should expand alone (hub
   // keys) -> output-balanced expansion
   const char* fb = env_str("DAS_DJ_BALANCED");        // tests: force either expansion
@@ -2481,24 +2491,39 @@ std::unique_ptr<Table> dj_expand(Ctx& c, const Table& P, const uint32_t* pkey, u
   // of 10^5 anchors x 10^2 links each): its few hundred waves would each
   // expand thousands of outputs while most of the chip idles
   const bool fanout = total >= (1ull << 14) && total / kBalChunk > 2 * units;
-  const bool balanced = fb ? fb[0] == '1' : (tm[1] > kHeavyUnit || fanout);
-  auto out = new_table(c, DAS_TABLE_ORDERED, nu, uni, total);
-  out->nrows = total;
-  if (total) {
-    // algorithmic bytes: probe payload + build payload +
-    // output, per launch (a schema wider than 4 + 4 columns is written by
-    // several launches, each reading the key and its own columns)
-    const bool one = jc.np <= 4 && jc.nb <= 4;
-    // build_bytes < 0: -(bytes per output) -- an index join reads one P row per output
-    if (build_bytes < 0) build_bytes = -build_bytes * (double)total;
-    auto bytes = [&](int np, int nb) {
-      if (one) return 4.0 * P.nrows * P.ncols + build_bytes + 4.0 * total * nu;
-      return 4.0 * P.nrows * (np + 1) + (jc.nb ? build_bytes * nb / jc.nb : 0.0) + 4.0 * total * (np + nb);
-    };
-    dj_write(grid, c.s, pkey, P.nrows, kmin, (uint32_t)range, lc, units, (const uint64_t*)toff.p, jc,
-             out->data, out->cap, total, balanced, bytes);
-    DAS_HIP(hipGetLastError());
-  }
+  k.balanced = fb ? fb[0] == '1' : (tm[1] > kHeavyUnit || fanout);
+  return k;
+}
+
+// The expansion's write pass: k.total rows of nu columns (stride cap) at
+// `data`, from np probe rows of pncols columns.
+void dj_write_rows(Ctx& c, uint64_t np, int pncols, const uint32_t* pkey, uint32_t kmin, uint64_t range,
+                   const uint2* lc, const DjCount& k, const JoinCols& jc, int nu, double build_bytes, uint32_t* data,
+                   uint64_t cap) {
+  const uint64_t total = k.total;
+  if (!total) return;
+  // algorithmic bytes: probe payload + build payload +
+  // output, per launch (a schema wider than 4 + 4 columns is written by
+  // several launches, each reading the key and its own columns)
+  const bool one = jc.np <= 4 && jc.nb <= 4;
+  // build_bytes < 0: -(bytes per output) -- an index join reads one P row per output
+  if (build_bytes < 0) build_bytes = -build_bytes * (double)total;
+  auto bytes = [&](int npc, int nbc) {
+    if (one) return 4.0 * np * pncols + build_bytes + 4.0 * total * nu;
+    return 4.0 * np * (npc + 1) + (jc.nb ? build_bytes * nbc / jc.nb : 0.0) + 4.0 * total * (npc + nbc);
+  };
+  dj_write(k.grid, c.s, pkey, np, kmin, (uint32_t)range, lc, k.units, (const uint64_t*)k.toff.p, jc, data, cap, total,
+           k.balanced, bytes);
+  DAS_HIP(hipGetLastError());
+}
+
+std::unique_ptr<Table> dj_expand(Ctx& c, const Table& P, const uint32_t* pkey, uint32_t kmin, uint64_t range,
+                                 const uint2* lc, const JoinCols& jc, int nu, const int32_t* uni,
+                                 double build_bytes) {
+  const DjCount k = dj_count(c, P, pkey, kmin, range, lc, jc);
+  auto out = new_table(c, DAS_TABLE_ORDERED, nu, uni, k.total);
+  out->nrows = k.total;
+  dj_write_rows(c, P.nrows, P.ncols, pkey, kmin, range, lc, k, jc, nu, build_bytes, out->data, out->cap);
   return out;
 }
 
@@ -3306,7 +3331,26 @@ std::unique_ptr<Table> anti_index_join(Ctx& c, const Table& A, const das_link_sc
   return compact_table(c, A, keep.p);
 }
 
-std::unique_ptr<Table> index_join(Ctx& c, const Table& A, const das_link_scan_t& q) {
+// A deferred index-join expansion (Lazy::EXPAND): index_join's state between
+// dj_count and dj_write_rows.  jc.p points into `probe`'s columns, jc.b into
+// index columns (so the record is listed in Ctx::aliases).
+struct Expansion {
+  std::unique_ptr<Table> probe;      // the probe rows (the plan's table, moved here)
+  DBuf<uint2> lc;                    // (first, count) of each probe row's index rows
+  DBuf<uint32_t> rowid;              // k_ij_lc's row ids: the write's pkey
+  DjCount k;
+  JoinCols jc{};
+  int nu = 0;
+};
+void ExpansionDel::operator()(Expansion* e) const { delete e; }
+
+bool defer_join_rows(uint64_t probe_rows, uint64_t out_rows) {
+  const char f = env_char("DAS_DEFER_JOIN");
+  if (f == '0') return false;
+  return f == '1' || (out_rows > (1ull << 20) && 4 * probe_rows <= out_rows);
+}
+
+std::unique_ptr<Table> index_join(Ctx& c, const Table& A, const das_link_scan_t& q, std::unique_ptr<Table>* take) {
   IjPlan pl;
   if (!ij_prepare(c, A, q, A.nrows, pl)) return nullptr;
   const int nu = (int)pl.uni.size();
@@ -3363,9 +3407,31 @@ std::unique_ptr<Table> index_join(Ctx& c, const Table& A, const das_link_scan_t&
         hipLaunchKernelGGL(k_ij_lc, G(A.nrows), dim3(B), 0, c.s, pl.akey, A.nrows, pl.kx, pl.g, lc.p, rowid.p);
         DAS_HIP(hipGetLastError());
       }
-      // build bytes: the P_{a,p} rows each output reads (4 B per fresh column;
-      // every output is its own P row, so the expansion sizes them)
-      out = dj_expand(c, A, rowid.p, 0u, A.nrows, lc.p, pl.jc, nu, pl.uni.data(), -4.0 * pl.jc.nb);
+      DjCount k = dj_count(c, A, rowid.p, 0u, A.nrows, lc.p, pl.jc);
+      if (take && take->get() == &A && !A.lazy && k.total && defer_join_rows(A.nrows, k.total)) {
+        // nothing reads these rows before the plan's answer does: the write
+        // pass is left to whatever reads them first (settle)
+        out = std::make_unique<Table>();         // new_table without the columns
+        out->ncols = nu;
+        for (int i = 0; i < nu; ++i) {
+          out->vars[i] = pl.uni[i];
+          out->member[i] = -1;
+        }
+        out->s = c.s;
+        out->nrows = k.total;
+        auto r = std::make_shared<Lazy>();
+        r->kind = Lazy::EXPAND;
+        r->ctx = &c;
+        r->exp.reset(new Expansion{std::move(*take), std::move(lc), std::move(rowid), std::move(k), pl.jc, nu});
+        out->lazy = std::move(r);
+      } else {
+        out = new_table(c, DAS_TABLE_ORDERED, nu, pl.uni.data(), k.total);
+        out->nrows = k.total;
+        // build bytes: the P_{a,p} rows each output reads (4 B per fresh column;
+        // every output is its own P row, so the expansion sizes them)
+        dj_write_rows(c, A.nrows, A.ncols, rowid.p, 0u, A.nrows, lc.p, k, pl.jc, nu, -4.0 * pl.jc.nb, out->data,
+                      out->cap);
+      }
     }
   }
   out->sorted_col = A.sorted_col >= 0 && !unsorted ? colof_t(*out, A.vars[A.sorted_col]) : -1;
@@ -4967,7 +5033,7 @@ void launch_cartesian(Ctx& c, const OutMap& om, uint64_t np, uint64_t nb, uint64
 }
 
 OutMap product_map(const Table& t) {
-  const Product& r = *t.prod;
+  const Lazy& r = *t.lazy;
   OutMap om{};
   om.n = t.ncols;
   for (int k = 0; k < t.ncols; ++k) {
@@ -4979,7 +5045,7 @@ OutMap product_map(const Table& t) {
 
 // a factor of a deferred product as a table over the record's columns
 Table factor_view(const Table& t, int side) {
-  const Product& r = *t.prod;
+  const Lazy& r = *t.lazy;
   Table f;
   f.kind = DAS_TABLE_ORDERED;
   f.ncols = side ? r.ncb : r.ncp;
@@ -4993,31 +5059,84 @@ Table factor_view(const Table& t, int side) {
 }
 }  // namespace
 
-void resolve_product(Ctx& c, Table& t) {
-  if (!t.prod) return;
-  const std::shared_ptr<Product> r = t.prod;            // alive until the launch is made
-  const OutMap om = product_map(t);
+void register_alias(Table& t) {
+  if (!t.lazy || !t.lazy->aliases_index() || t.lazy->owner) return;
+  t.lazy->owner = &t;
+  t.lazy->ctx->aliases.push_back(t.lazy.get());
+  t.lazy->listed.store(true, std::memory_order_release);
+}
+
+void deregister_alias(Lazy& r) {
+  if (!r.owner) return;
+  auto& v = r.ctx->aliases;
+  v.erase(std::remove(v.begin(), v.end(), &r), v.end());
+  r.owner = nullptr;
+  r.listed.store(false, std::memory_order_release);
+}
+
+void settle_aliases(Ctx& c) {
+  // (settle takes each record off the list)
+  while (!c.aliases.empty()) settle(c, *c.aliases.back()->owner);
+}
+
+void make_lazy_view(Ctx& c, Table& t) {
+  DAS_CHECK(t.view && !t.lazy, DAS_E_INTERNAL, "make_lazy_view: not a view");
+  auto r = std::make_shared<Lazy>();
+  r->kind = Lazy::VIEW;
+  r->ctx = &c;
+  t.lazy = std::move(r);
+}
+
+void settle(Ctx& c, Table& t) {
+  if (!t.lazy) return;
+  const std::shared_ptr<Lazy> r = t.lazy;               // alive until the launch is made
   const uint64_t cap = col_stride(t.nrows ? t.nrows : 1);
   uint32_t* data = (uint32_t*)cache_alloc(4ull * t.ncols * cap, c.s);
-  t.prod.reset();
+  deregister_alias(*r);                                 // (after the allocation: a failed one leaves it listed)
+  if (r->kind == Lazy::PRODUCT) {
+    const OutMap om = product_map(t);
+    t.lazy.reset();
+    t.data = data;
+    t.cap = cap;
+    t.s = c.s;
+    launch_cartesian(c, om, r->np, r->nb, 0, t.nrows, t);
+    return;
+  }
+  if (r->kind == Lazy::VIEW) {
+    // the copy a plan's answer or das_scan_link made before it returned
+    const uint32_t* src = t.data;
+    const uint64_t ld = t.cap;
+    for (int k = 0; k < t.ncols; ++k) copy_dev(data + (uint64_t)k * cap, src + (uint64_t)k * ld, 4 * t.nrows, c.s);
+    t.lazy.reset();
+    t.view = false;
+    t.data = data;
+    t.cap = cap;
+    t.s = c.s;
+    return;
+  }
+  const Expansion& e = *r->exp;
+  t.lazy.reset();
   t.data = data;
   t.cap = cap;
   t.s = c.s;
-  launch_cartesian(c, om, r->np, r->nb, 0, t.nrows, t);
+  // build bytes: the P_{a,p} rows each output reads (4 B per fresh column;
+  // every output is its own P row, so the expansion sizes them)
+  dj_write_rows(c, e.probe->nrows, e.probe->ncols, e.rowid.p, 0u, e.probe->nrows, e.lc.p, e.k, e.jc, e.nu,
+                -4.0 * e.jc.nb, data, cap);
 }
 
 std::unique_ptr<Table> product_rows(Ctx& c, const Table& t, uint64_t row0, uint64_t n) {
-  DAS_CHECK(t.prod, DAS_E_INTERNAL, "product_rows: not a deferred product");
+  DAS_CHECK(t.lazy && t.lazy->kind == Lazy::PRODUCT, DAS_E_INTERNAL, "product_rows: not a deferred product");
   DAS_CHECK(row0 <= t.nrows && n <= t.nrows - row0, DAS_E_INVALID, "rows out of range");
   auto out = new_table(c, DAS_TABLE_ORDERED, t.ncols, t.vars, n);
   out->nrows = n;
-  if (n) launch_cartesian(c, product_map(t), t.prod->np, t.prod->nb, row0, n, *out);
+  if (n) launch_cartesian(c, product_map(t), t.lazy->np, t.lazy->nb, row0, n, *out);
   return out;
 }
 
 void product_checksum(Ctx& c, const Table& t, const uint64_t* salt, uint64_t out[2]) {
-  DAS_CHECK(t.prod, DAS_E_INTERNAL, "product_checksum: not a deferred product");
-  const Product& r = *t.prod;
+  DAS_CHECK(t.lazy && t.lazy->kind == Lazy::PRODUCT, DAS_E_INTERNAL, "product_checksum: not a deferred product");
+  const Lazy& r = *t.lazy;
   // a row's value is the product of its columns' values, so the rows' sum is
   // (sum over P of its columns' product) * (sum over Q of its columns' product)
   uint64_t sp[kMaxCols] = {0}, sb[kMaxCols] = {0};
@@ -5059,7 +5178,7 @@ std::unique_ptr<Table> join(Ctx& c, const Table& A, const Table& Bt, int no_over
     }
     out->s = c.s;
     out->nrows = total;
-    auto r = std::make_shared<Product>();
+    auto r = std::make_shared<Lazy>();
     r->ctx = &c;
     r->np = P.nrows;
     r->nb = Q.nrows;
@@ -5081,7 +5200,7 @@ std::unique_ptr<Table> join(Ctx& c, const Table& A, const Table& Bt, int no_over
       r->side[k] = ip >= 0 ? 0 : 1;
       r->src[k] = (uint8_t)(ip >= 0 ? ip : colof(Q, uni[k]));
     }
-    out->prod = std::move(r);
+    out->lazy = std::move(r);
   } else if (shared.empty()) {
     const uint64_t total = P.nrows * Q.nrows;
     out = new_table(c, DAS_TABLE_ORDERED, nu, uni.data(), total);

@@ -482,7 +482,21 @@ int das_table_info(const das_table_t* t, int32_t* kind, int32_t* ncols, int32_t*
  * host fields, das_table_fetch expands only the rows asked for,
  * das_table_checksum multiplies the factors' sums, and every other call that
  * takes the table expands it first, once (das_table_column with the context
- * that made it).  The rows and their order are those of the written product. */
+ * that made it).  The rows and their order are those of the written product.
+ *
+ * Two more answers keep their rows unwritten (DAS_DEFER_JOIN=0 never, =1 at
+ * every size, unset: above 2^20 rows): a plan's final index join stopped
+ * after its count pass, and a das_scan_link / lone-Link plan answer that is a
+ * range of index columns.  das_table_info / bounds / members never write
+ * them; das_table_fetch reads a scan answer in place; das_table_fetch and
+ * das_table_checksum of a deferred join, and every other call that takes the
+ * table, write the rows first, once -- through the context that made the
+ * answer (another context: DAS_ERR_INVALID).  Both read index arrays, so the
+ * context lists them: das_build_index*, and das_ctx_destroy, first write the
+ * rows of every listed answer still alive (the rows the old index gave), then
+ * release the arrays -- a rebuild with live unread answers costs what the
+ * eager path held all along.  das_table_free of an unwritten answer takes
+ * its context's lock and frees the record alone. */
 /* Copies rows [row0, row0+nrows) column-major into host `out` (ncols*nrows). */
 int das_table_fetch(das_ctx_t* ctx, const das_table_t* t, uint64_t row0, uint64_t nrows,
                     uint32_t* out);
