@@ -81,6 +81,7 @@ NAME_STAGE_BYTES = 16384          # DAS_NAME_STAGE_BYTES: name bytes of one tile
 NAME_FILTER_AUTO, NAME_FILTER_WALK, NAME_FILTER_FLAGS = 0, 1, 2   # DAS_NAME_FILTER_*: das_table_name_filter's mode
 NAME_COPY_WAVE = 64               # DAS_NAME_COPY_WAVE: a longer name is copied by a whole wave
 NAME_FETCH_GUESS = 32             # Context.node_names: bytes per name of the first call's capacity
+GROUP_GUESS = 1 << 16             # Context.group_counts: groups of the first call's capacity at most
 DOC_MAX_DEPTH = 16                # DAS_DOC_MAX_DEPTH: levels of a deep representation das_atoms_json renders
 DOC_GUESS = 512                   # Context.atoms_json: bytes per root of the first call's capacity
 HALO_MAX_LEVELS = 8               # DAS_HALO_MAX_LEVELS
@@ -136,6 +137,7 @@ _SIGS = {
     "das_table_name_filter": (C.c_int, [P, P, C.c_int32, C.c_uint32, P, C.c_int32, C.POINTER(P)]),
     "das_node_name_stats": (C.c_int, [P, C.c_uint32, P, P, P]),
     "das_node_names": (C.c_int, [P, P, C.c_uint64, P, C.c_int32, C.c_uint64, P, P, C.c_uint64, P, P, P]),
+    "das_group_counts": (C.c_int, [P, P, P, C.c_uint32, P, P, C.c_uint64, P, P]),
     "das_atoms_json": (C.c_int, [P, P, C.c_uint64, P, C.c_int32, C.c_uint64, C.c_uint32, P, P, C.c_uint32, P,
                                  C.c_uint64, P, P, P]),
     "das_links_outgoing": (C.c_int, [P, P, C.c_uint64, P, C.c_int32, C.c_uint64, P, P, C.c_uint64, P, P, P]),
@@ -690,6 +692,38 @@ class Context:
                 break
             cap, guess = total.value, False
         return off, buf[:min(total.value, cap)], kind[:n]
+
+    def group_counts(self, tables, cols, cap=None):
+        """(ids, counts, stats) of das_group_counts: over column cols[i] of
+        the ordered device Table tables[i], the distinct values (uint32,
+        ascending) and the rows that hold each (uint64), summed over the
+        tables; stats = (tables counted unwritten, tables settled).  cap: the
+        groups to make room for (default: a guess, and a second call with the
+        number reported where it was short, which copies the kept result)."""
+        tables, cols = list(tables), [int(c) for c in cols]
+        if len(tables) != len(cols):
+            raise ValueError("group_counts: one column per table")
+        n = len(tables)
+        th = (C.c_void_p * max(n, 1))(*[t.h for t in tables])
+        cc = np.ascontiguousarray(cols, dtype=np.int32)
+        guess = cap is None
+        cap = min(sum(t.nrows for t in tables), GROUP_GUESS) if guess else int(cap)
+        if cap < 0:
+            raise ValueError("group_counts: negative cap")
+        total = C.c_uint64()
+        stats = np.zeros(2, dtype=np.uint64)
+        seen = np.zeros(2, dtype=np.uint64)
+        while True:
+            ids = np.empty(max(cap, 1), dtype=np.uint32)
+            counts = np.empty(max(cap, 1), dtype=np.uint64)
+            rc = lib().das_group_counts(self.h, th, ptr(cc), n, ptr(ids), ptr(counts), cap, C.byref(total),
+                                        ptr(seen))
+            stats += seen
+            if rc == ERR_INVALID and guess and total.value > cap:
+                cap, guess = total.value, False
+                continue
+            check(rc, self.h)
+            return ids[:total.value], counts[:total.value], (int(stats[0]), int(stats[1]))
 
     @staticmethod
     def _entries(what, ids, table, col, row0, nrows):

@@ -25,6 +25,9 @@ struct das_table {
   // so that das_table_free finds the context without reading t.lazy, which
   // a rebuild on another thread may be dropping
   std::shared_ptr<das::Lazy> reg;
+  // non-zero: the mark das_group_counts gave this handle when it kept a
+  // result over it (a later handle at the same address has none)
+  mutable uint64_t group_mark = 0;
 };
 struct das_parsed {
   std::unique_ptr<das::Parsed> p;
@@ -33,6 +36,9 @@ struct das_parsed {
 namespace {
 
 thread_local std::string g_err;   // errors without a context
+
+// marks of the handles a kept das_group_counts result names (das_table::group_mark)
+std::atomic<uint64_t> g_group_mark{0};
 
 int fail(das_ctx_t* ctx, int code, const std::string& msg) {
   if (ctx) ctx->c.err = msg;
@@ -575,6 +581,51 @@ int das_node_names(das_ctx_t* ctx, const uint32_t* ids, uint64_t n, const das_ta
       d_ids = settled(ctx, table).col(col) + row0;
     }
     *n_bytes = das::node_names(ctx->c, table ? nullptr : ids, d_ids, n, off, bytes, cap, kind, n_other);
+  });
+}
+
+int das_group_counts(das_ctx_t* ctx, const das_table_t* const* ts, const int32_t* cols, uint32_t n,
+                     uint32_t* out_ids, uint64_t* out_counts, uint64_t cap, uint64_t* n_groups, uint64_t stats[2]) {
+  if (!ctx || !n_groups || (n && (!ts || !cols)) || (cap && (!out_ids || !out_counts)))
+    return fail(ctx, DAS_ERR_INVALID, "null argument");
+  return guarded(ctx, [&] {
+    Ctx& c = ctx->c;
+    Ctx::GroupResult& g = c.group;
+    std::vector<Table*> tv(n);
+    std::vector<const void*> key(n);
+    std::vector<uint64_t> nr(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      DAS_CHECK(ts[i], das::DAS_E_INVALID, "null table");
+      tv[i] = const_cast<Table*>(&ts[i]->t);
+      key[i] = ts[i];
+      nr[i] = ts[i]->t.nrows;
+    }
+    uint64_t st[2] = {0, 0};
+    bool again = g.valid && g.tables == key && g.nrows == nr && g.cols == std::vector<int32_t>(cols, cols + n);
+    for (uint32_t i = 0; i < n && again; ++i) again = ts[i]->group_mark == g.mark;
+    if (!again) {
+      das::group_counts(c, tv.data(), cols, n, st);
+      g.tables = std::move(key);
+      g.cols.assign(cols, cols + n);
+      g.nrows = std::move(nr);
+      g.mark = g_group_mark.fetch_add(1, std::memory_order_relaxed) + 1;
+      for (uint32_t i = 0; i < n; ++i) ts[i]->group_mark = g.mark;
+      g.valid = true;
+    }
+    if (stats) {
+      stats[0] = st[0];
+      stats[1] = st[1];
+    }
+    *n_groups = g.n;
+    DAS_CHECK(g.n <= cap, das::DAS_E_INVALID, "group counts: capacity too small (call again with *n_groups)");
+    if (g.n) {
+      DAS_HIP(hipMemcpyAsync(out_ids, g.ids.p, 4 * g.n, hipMemcpyDeviceToHost, c.s));
+      DAS_HIP(hipMemcpyAsync(out_counts, g.counts.p, 8 * g.n, hipMemcpyDeviceToHost, c.s));
+    }
+    DAS_HIP(hipStreamSynchronize(c.s));
+    g.valid = false;
+    g.ids.release();
+    g.counts.release();
   });
 }
 

@@ -347,6 +347,20 @@ struct Ctx {
     }
     return side_ev[i];
   }
+  // the last das_group_counts result, kept on the device so that the call
+  // repeated with the capacity it reported copies instead of counting again:
+  // valid for the same handles (each carrying this result's mark: a handle
+  // freed and allocated again at the same address has none), columns and
+  // row counts
+  struct GroupResult {
+    bool valid = false;
+    std::vector<const void*> tables;
+    std::vector<int32_t> cols;
+    std::vector<uint64_t> nrows;
+    uint64_t mark = 0, n = 0;
+    DBuf<uint32_t> ids;
+    DBuf<uint64_t> counts;
+  } group;
   // loader-side host copies kept for metadata calls
   std::vector<uint8_t> leaf_bytes;
   std::vector<uint64_t> leaf_off;
@@ -547,6 +561,17 @@ void make_lazy_view(Ctx& c, Table& t);
 // Rows [row0, row0 + n) of a deferred product expanded into a table of n rows
 // (the product itself stays deferred).
 std::unique_ptr<Table> product_rows(Ctx& c, const Table& t, uint64_t row0, uint64_t n);
+// Output column `col` of a deferred expansion (Lazy::EXPAND) where the probe
+// table holds it: probe row r has key[r] and stands for lc[rowid[r]].y output
+// rows (the indexing the count pass left for the write).  false: the column is
+// a fresh variable the expansion reads from the index.
+struct ExpansionCol {
+  const uint32_t* key = nullptr;
+  const uint32_t* rowid = nullptr;
+  const uint2* lc = nullptr;
+  uint64_t n = 0;
+};
+bool expansion_probe_col(const Table& t, int col, ExpansionCol& out);
 // table_checksum of a deferred product from its factors' sums.
 void product_checksum(Ctx& c, const Table& t, const uint64_t* salt, uint64_t out[2]);
 // rows of p whose value of the one shared variable lies in EVERY qs[i]'s key
@@ -674,6 +699,13 @@ int fused_or(Ctx& c, const std::vector<const das_plan_node_t*>& terms, int no_ov
 std::unique_ptr<UnionRun> fused_or_launch(Ctx& c, const std::vector<const das_plan_node_t*>& terms, int no_overload,
                                           uint32_t k, int side, hipEvent_t fence_in, bool* waited);
 int fused_or_finish(Ctx& c, UnionRun& u, bool& matched, std::unique_ptr<Table>& out);
+
+// group.hip: rows per value of one variable (das_group_counts).  For tables
+// ts[i] and their columns cols[i] (unresolved tables counted from what they
+// keep) the distinct values in ascending order and the rows
+// that hold each are left on the device in c.group; returns their number.
+// stats[0] += tables counted unwritten, stats[1] += tables settled.
+uint64_t group_counts(Ctx& c, Table* const* ts, const int32_t* cols, uint32_t n, uint64_t stats[2]);
 
 // export.hip: Redis key-space files (canonical_parser.py:119-183)
 struct ExportCounts {

@@ -3344,6 +3344,21 @@ struct Expansion {
 };
 void ExpansionDel::operator()(Expansion* e) const { delete e; }
 
+bool expansion_probe_col(const Table& t, int col, ExpansionCol& out) {
+  DAS_CHECK(t.lazy && t.lazy->kind == Lazy::EXPAND && t.lazy->exp, DAS_E_INTERNAL,
+            "expansion_probe_col: not a deferred expansion");
+  const Expansion& e = *t.lazy->exp;
+  for (int j = 0; j < e.jc.np; ++j) {
+    if (e.jc.po[j] != col) continue;
+    out.key = e.jc.p[j];
+    out.rowid = e.rowid.p;
+    out.lc = e.lc.p;
+    out.n = e.probe->nrows;
+    return true;
+  }
+  return false;
+}
+
 bool defer_join_rows(uint64_t probe_rows, uint64_t out_rows) {
   const char f = env_char("DAS_DEFER_JOIN");
   if (f == '0') return false;

@@ -145,6 +145,11 @@ class HipDB(RelationalDB):
     ATOM_DOCS_MIN = 1
     ATOM_DOCS_MIN_PREFETCHED = 1
     ATOM_DOCS_MIN_NODES = 2
+    # answer.value_counts: answers of fewer rows than this take the host Counter.  Measured on the bench's bio KB
+    # (profiles/group_counts.json): the device call takes 0.13 ms at 1 row and 0.18 ms from 4 to 256
+    # rows; the Counter over freshly built Assignment objects 0.09 ms up to 16 rows, 0.12 ms at 64 and 0.29 ms at
+    # 256, the first size measured from which the device call is never slower (0.19 against 0.94 ms at 1024).
+    GROUP_MIN = 256
 
     def __init__(self, device: int = 0, stream=None, tuple_targets: bool = False,
                  stale_pattern_keys: bool = False):
@@ -203,6 +208,8 @@ class HipDB(RelationalDB):
         self.mine_stats = {"device": 0, "host": 0}          # mine: calls answered by each path
         self.atom_docs_stats = {"device": 0, "host": 0}     # atoms_json / get_atoms_as_dicts: calls of each path
         self.name_term_stats = {"device": 0, "host": 0}     # NameMatch terms evaluated by each path
+        # answer.value_counts: calls answered by each path; tables counted without writing their rows / settled
+        self.group_stats = {"device": 0, "host": 0, "unwritten": 0, "settled": 0}
         self._type_json = None          # das_atoms_json's type texts, per load
         self._template_cache = {}       # composite-type id -> template of its links, per load
 

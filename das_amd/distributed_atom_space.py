@@ -9,7 +9,7 @@ names and behaviour.
 import json
 import os
 from enum import Enum, auto
-from typing import Dict, List, Tuple, Union
+from typing import Dict, List, Optional, Tuple, Union
 
 import numpy as np
 
@@ -274,6 +274,24 @@ class DistributedAtomSpace:
         if not query.matched(self.db, query_answer):
             return []
         return query_answer.names(variable, db=self.db)
+
+    def value_counts(self, query: LogicalExpression, variable: str, top: Optional[int] = None,
+                     names: bool = False):
+        """The rows of the query's answer per value of `variable`, evaluated
+        as get_mappings evaluates it: a pattern_matcher.ValueCounts (an empty
+        one where the query does not match), counted on the device without
+        writing the answer's rows where it is still unresolved
+        (PatternMatchingAnswer.value_counts).  top: its most_common(top)
+        instead, (handle, count) pairs by count descending; names: (node
+        name, count) pairs."""
+        query_answer = PatternMatchingAnswer()
+        if not query.matched(self.db, query_answer):
+            query_answer = PatternMatchingAnswer()
+            query_answer.assignments = set()
+        vc = query_answer.value_counts(variable, db=self.db)
+        if top is None and not names:
+            return vc
+        return vc.most_common(top, names=names)
 
     # -- pattern miner (notebooks/SimplePatternMiner.ipynb cells 6 and 5) ----
     def halo(self, seeds: List[str], length: int = 2):

@@ -807,6 +807,138 @@ class PatternMatchingAnswer:
             db.name_fetch_stats["host"] += 1
         return names_host(db, self, variable, strict)
 
+    def value_counts(self, variable, db=None) -> "ValueCounts":
+        """The answer's rows per value of one variable: a ValueCounts whose
+        `total` is count().  A variable the answer does not bind raises
+        KeyError.
+
+        Device path -- the answer still holds its device relation, every
+        local table is ordered and binds the variable and the DB is a HipDB:
+        one das_group_counts call over the tables where they lie.  An
+        unresolved answer (a deferred product, index join or scan view) is
+        counted from what it keeps, without writing its rows; only a
+        deferred index join grouped by a variable its expansion reads from
+        the index writes them first.  Everything else (unordered or
+        composite tables, hand-set assignments, a sharded DB, DAS_GROUP=0,
+        fewer rows than HipDB.GROUP_MIN) runs value_counts_host.
+        `db.group_stats` counts the calls of each path and the tables counted
+        unwritten and settled.  `db`: the DB of an answer whose assignments
+        were set by hand."""
+        db = db if db is not None else self._db
+        if db is None:
+            if self._py is None or self._py:
+                raise ValueError("value_counts: the answer holds no database")
+            return ValueCounts(db, counter=Counter())
+        if (self._rel is not None and db is self._db and isinstance(db, HipDB)
+                and os.environ.get("DAS_GROUP", "1") != "0"):
+            tables = [t for t in db.rel_local_tables(self._rel) if t.nrows]
+            if (all(t.kind == _lib.TABLE_ORDERED for t in tables)
+                    and sum(t.nrows for t in tables) >= db.GROUP_MIN):
+                cols = []
+                for t in tables:
+                    bound = [_var_name(v) for v in t.vars]
+                    if variable not in bound:
+                        raise KeyError(variable)
+                    cols.append(bound.index(variable))
+                ids, counts, (unwritten, settled) = db.ctx.group_counts(tables, cols)
+                db.group_stats["device"] += 1
+                db.group_stats["unwritten"] += unwritten
+                db.group_stats["settled"] += settled
+                return ValueCounts(db, ids=ids, counts=counts)
+        if hasattr(db, "group_stats"):
+            db.group_stats["host"] += 1
+        return ValueCounts(db, counter=value_counts_host(db, self, variable))
+
+    def distinct(self, variable, db=None) -> List[str]:
+        """The handles of the distinct values of one variable; order
+        unspecified (ascending atom id on the device path of value_counts,
+        sorted by handle on the host path)."""
+        return list(self.value_counts(variable, db=db).handles)
+
+
+def value_counts_host(db, answer, variable):
+    """The definition of PatternMatchingAnswer.value_counts, over any
+    DBInterface: Counter(a.mapping[variable] for a in answer.assignments),
+    handle -> rows.  An assignment without a `mapping` (unordered, composite)
+    raises AttributeError and a row that does not bind the variable
+    KeyError(variable), as names_host does."""
+    out = Counter()
+    for a in answer.assignments:
+        out[a.mapping[variable]] += 1
+    return out
+
+
+class ValueCounts:
+    """Distinct values of one variable of an answer and the rows that hold
+    each.  Built from atom ids (the device path: `ids` uint32 ascending,
+    `counts` uint64) or from a Counter handle -> rows (the host path: `ids`
+    is None, the handles sorted)."""
+
+    def __init__(self, db, ids=None, counts=None, counter=None):
+        self._db = db
+        if counter is not None:
+            self.ids = None
+            self._handles = sorted(counter)
+            self.counts = np.array([counter[h] for h in self._handles], dtype=np.uint64)
+        else:
+            self.ids = np.asarray(ids, dtype=np.uint32)
+            self.counts = np.asarray(counts, dtype=np.uint64)
+            self._handles = None
+
+    @property
+    def handles(self) -> List[str]:
+        """The values as 32-hex handles (db.hex_of), built on first access."""
+        if self._handles is None:
+            self._handles = list(self._db.hex_of(self.ids)) if len(self.ids) else []
+        return self._handles
+
+    def __len__(self):
+        return len(self.counts)
+
+    @property
+    def total(self) -> int:
+        return int(self.counts.sum(dtype=np.uint64)) if len(self.counts) else 0
+
+    def names(self, strict=True) -> List[Optional[str]]:
+        """get_node_name of every value, in the order of `handles`: one bulk
+        db.get_node_names call where the DB has it."""
+        if not len(self):
+            return []
+        if hasattr(self._db, "get_node_names"):
+            return list(self._db.get_node_names(self.ids if self.ids is not None else self.handles, strict=strict))
+        out = []
+        for h in self.handles:
+            try:
+                out.append(self._db.get_node_name(h))
+            except ValueError:
+                if strict:
+                    raise
+                out.append(None)
+        return out
+
+    def _order(self, k=None):
+        # by count descending, ties by handle ascending
+        handles = self.handles
+        order = sorted(range(len(handles)), key=lambda i: (-int(self.counts[i]), handles[i]))
+        return order if k is None else order[:max(int(k), 0)]
+
+    def most_common(self, k=None, names=False):
+        """(handle, count) pairs by count descending, ties by handle
+        ascending (the same on both paths); the first k of them.  names:
+        (node name, count) pairs instead."""
+        order = self._order(k)
+        if names:
+            if self.ids is not None and hasattr(self._db, "get_node_names"):
+                keys = list(self._db.get_node_names(self.ids[order], strict=True)) if order else []
+            else:
+                keys = [self._db.get_node_name(self.handles[i]) for i in order]
+        else:
+            keys = [self.handles[i] for i in order]
+        return [(key, int(self.counts[i])) for key, i in zip(keys, order)]
+
+    def as_dict(self) -> Dict[str, int]:
+        return {h: int(n) for h, n in zip(self.handles, self.counts)}
+
 
 def names_host(db, answer, variable=None, strict=True):
     """The definition of PatternMatchingAnswer.names, over any DBInterface:

@@ -282,6 +282,19 @@ int das_node_names(das_ctx_t* ctx, const uint32_t* ids, uint64_t n, const das_ta
                    uint64_t row0, uint64_t* off, uint8_t* bytes, uint64_t cap, uint8_t* kind, uint64_t* n_bytes,
                    uint64_t* n_other);
 
+/* Rows of the answer per value of one variable: for tables ts[i] (ORDERED) and
+ * their columns cols[i], the distinct values in ascending id order and the
+ * number of rows that hold each, summed over the tables.  Unresolved answers
+ * (see das_table_fetch) are counted from what they keep; only a deferred index
+ * join grouped by a variable its expansion reads from the index writes its rows
+ * first.  DAS_ERR_INVALID with *n_groups set when cap is too small (call again),
+ * when a table is not ORDERED, or when a column is out of range.  The result
+ * stays on the device until the next call: the call repeated with the capacity
+ * reported copies it and does not count again. */
+int das_group_counts(das_ctx_t* ctx, const das_table_t* const* ts, const int32_t* cols, uint32_t n,
+                     uint32_t* out_ids, uint64_t* out_counts, uint64_t cap, uint64_t* n_groups,
+                     uint64_t stats[2] /* tables counted unwritten, tables settled */);
+
 /* ---- atom documents in bulk (redis_mongo_db.py:187-199, 297-314) ---------- */
 #define DAS_DOC_MAX_DEPTH 16 /* levels of a deep representation (a root is level 1) */
 /* json.dumps(deep representation, sort_keys=False, indent=4) of n atoms as
