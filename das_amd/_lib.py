@@ -84,6 +84,9 @@ NAME_FETCH_GUESS = 32             # Context.node_names: bytes per name of the fi
 GROUP_GUESS = 1 << 16             # Context.group_counts: groups of the first call's capacity at most
 DOC_MAX_DEPTH = 16                # DAS_DOC_MAX_DEPTH: levels of a deep representation das_atoms_json renders
 DOC_GUESS = 512                   # Context.atoms_json: bytes per root of the first call's capacity
+ROWS_TEXT_STAGE_BYTES = 16384     # DAS_ROWS_TEXT_STAGE_BYTES: bytes of one tile's image of das_table_rows_text
+ROWS_TEXT_MAX_ROW = ROWS_TEXT_STAGE_BYTES - 16   # DAS_ROWS_TEXT_MAX_ROW: a row's text and its separator at most
+ROWS_TEXT_HEX = 32                # characters of a handle: what das_table_rows_text puts into each hole
 HALO_MAX_LEVELS = 8               # DAS_HALO_MAX_LEVELS
 HALO_BLOCK_ENTRIES = 1024         # DAS_HALO_BLOCK_ENTRIES: incoming-list entries one workgroup marks per pass
 PC_CHUNK_ROWS = 1024              # DAS_PC_CHUNK_ROWS: index rows one wave counts per step of a (1,2)-grounded template
@@ -137,6 +140,7 @@ _SIGS = {
     "das_table_name_filter": (C.c_int, [P, P, C.c_int32, C.c_uint32, P, C.c_int32, C.POINTER(P)]),
     "das_node_name_stats": (C.c_int, [P, C.c_uint32, P, P, P]),
     "das_node_names": (C.c_int, [P, P, C.c_uint64, P, C.c_int32, C.c_uint64, P, P, C.c_uint64, P, P, P]),
+    "das_table_rows_text": (C.c_int, [P, P, C.c_uint64, C.c_uint64, P, P, P, C.c_uint32, P, C.c_uint64, P, P]),
     "das_group_counts": (C.c_int, [P, P, P, C.c_uint32, P, P, C.c_uint64, P, P]),
     "das_atoms_json": (C.c_int, [P, P, C.c_uint64, P, C.c_int32, C.c_uint64, C.c_uint32, P, P, C.c_uint32, P,
                                  C.c_uint64, P, P, P]),
@@ -367,6 +371,15 @@ def decode_names(off, data, kind):
         for i in np.flatnonzero(kind == 0).tolist():
             out[i] = None
     return out
+
+
+def rows_text_size(lits, sep, nrows):
+    """Bytes of Context.rows_text's text of `nrows` rows: every row is its
+    literal pieces and one 32-hex handle per column."""
+    if nrows <= 0:
+        return 0
+    row = sum(len(x) for x in lits) + ROWS_TEXT_HEX * (len(lits) - 1)
+    return nrows * row + (nrows - 1) * len(sep)
 
 
 class Table:
@@ -724,6 +737,49 @@ class Context:
                 continue
             check(rc, self.h)
             return ids[:total.value], counts[:total.value], (int(stats[0]), int(stats[1]))
+
+    def rows_text(self, table, lits, sep, row0=0, nrows=None, cap=None, out=None):
+        """(bytes, total, n_bad) of das_table_rows_text: rows [row0, row0 +
+        nrows) (default: to the end) of the ordered device Table as text, a
+        uint8 array of min(total, cap) bytes.  lits: the ncols + 1 literal
+        pieces (bytes) around the columns' 32-hex handles, sep: the bytes
+        between rows.  total: the text's true size, known before the call
+        (rows_text_size); cap: copy at most that many bytes (default: all);
+        out: a uint8 array to copy into.  n_bad: cells that are no atom's id
+        (non-zero: the text is unspecified).  None instead of the tuple where
+        a row with its separator exceeds ROWS_TEXT_MAX_ROW bytes
+        (DAS_ERR_LIMIT)."""
+        lits = [bytes(x) for x in lits]
+        sep = bytes(sep)
+        if len(lits) != len(table.vars) + 1:
+            raise ValueError("rows_text: one literal piece more than the table has columns")
+        row0 = int(row0)
+        n = table.nrows - row0 if nrows is None else int(nrows)
+        if row0 < 0 or row0 > table.nrows or n < 0 or n > table.nrows - row0:
+            raise ValueError("rows_text: rows out of range")
+        size = rows_text_size(lits, sep, n)
+        if out is not None:
+            if out.dtype != np.uint8 or not out.flags.c_contiguous or out.ndim != 1:
+                raise ValueError("rows_text: out must be a contiguous uint8 array")
+            if cap is None:
+                cap = out.size
+            elif int(cap) > out.size:
+                raise ValueError("rows_text: cap exceeds the out buffer")
+        cap = size if cap is None else int(cap)
+        if cap < 0:
+            raise ValueError("rows_text: negative cap")
+        lit = np.frombuffer(b"".join(lits) or b"\0", dtype=np.uint8)
+        off = np.zeros(len(lits) + 1, dtype=np.uint32)
+        np.cumsum([len(x) for x in lits], out=off[1:])
+        sp = np.frombuffer(sep or b"\0", dtype=np.uint8)
+        buf = out if out is not None else np.empty(max(min(cap, size), 1), dtype=np.uint8)
+        total, bad = C.c_uint64(), C.c_uint64()
+        rc = lib().das_table_rows_text(self.h, table.h, row0, n, ptr(lit), ptr(off), ptr(sp), len(sep), ptr(buf),
+                                       min(cap, size) if out is None else cap, C.byref(total), C.byref(bad))
+        if rc == ERR_LIMIT:
+            return None
+        check(rc, self.h)
+        return buf[:min(total.value, cap)], total.value, bad.value
 
     @staticmethod
     def _entries(what, ids, table, col, row0, nrows):

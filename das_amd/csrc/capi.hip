@@ -629,6 +629,16 @@ int das_group_counts(das_ctx_t* ctx, const das_table_t* const* ts, const int32_t
   });
 }
 
+int das_table_rows_text(das_ctx_t* ctx, const das_table_t* t, uint64_t row0, uint64_t nrows, const uint8_t* lit,
+                        const uint32_t* lit_off, const uint8_t* sep, uint32_t sep_len, uint8_t* out, uint64_t cap,
+                        uint64_t* n_bytes, uint64_t* n_bad) {
+  if (!ctx || !t || !n_bytes) return fail(ctx, DAS_ERR_INVALID, "null argument");
+  return guarded(ctx, [&] {
+    *n_bytes = das::table_rows_text(ctx->c, const_cast<Table&>(t->t), row0, nrows, lit, lit_off, sep, sep_len, out,
+                                    cap, n_bad);
+  });
+}
+
 // the ids of a document call: rows [row0, row0 + n) of a table column where they lie, else null (the host ids)
 static const uint32_t* doc_column(das_ctx_t* ctx, const das_table_t* table, int32_t col, uint64_t row0, uint64_t n) {
   if (!table) return nullptr;

@@ -707,6 +707,16 @@ int fused_or_finish(Ctx& c, UnionRun& u, bool& matched, std::unique_ptr<Table>& 
 // stats[0] += tables counted unwritten, stats[1] += tables settled.
 uint64_t group_counts(Ctx& c, Table* const* ts, const int32_t* cols, uint32_t n, uint64_t stats[2]);
 
+// rows_text.hip: the rows of an ordered table as text (das_table_rows_text,
+// DESIGN.md §3g).  Rows [row0, row0 + nrows) of `t`, each lit[0] hex(col0)
+// lit[1] .. lit[ncols] (lit_off: ncols + 2 offsets into lit), joined by `sep`;
+// returns the total, min(total, cap) bytes copied to the host array `out`,
+// *n_bad = cells whose id is no atom's.  An unresolved table is read from what
+// it keeps (VIEW, PRODUCT) or settled (EXPAND).  Throws DAS_E_LIMIT when a row
+// with its separator exceeds DAS_ROWS_TEXT_MAX_ROW bytes.
+uint64_t table_rows_text(Ctx& c, Table& t, uint64_t row0, uint64_t nrows, const uint8_t* lit, const uint32_t* lit_off,
+                         const uint8_t* sep, uint32_t sep_len, uint8_t* out, uint64_t cap, uint64_t* n_bad);
+
 // export.hip: Redis key-space files (canonical_parser.py:119-183)
 struct ExportCounts {
   uint64_t outgoing = 0, incoming = 0, patterns = 0, templates = 0, names = 0;

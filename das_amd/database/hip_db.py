@@ -150,6 +150,15 @@ class HipDB(RelationalDB):
     # rows; the Counter over freshly built Assignment objects 0.09 ms up to 16 rows, 0.12 ms at 64 and 0.29 ms at
     # 256, the first size measured from which the device call is never slower (0.19 against 0.94 ms at 1024).
     GROUP_MIN = 256
+    # answer.text / DistributedAtomSpace.query: answers of fewer rows than this format the set of Assignment
+    # objects as before.  Measured on the bench's bio KB (profiles/query_text.json): a two-variable
+    # answer takes 0.07 ms on the device at 1 to 16 rows, the host path 0.057 ms at 1 and 4 rows and 0.068 ms at
+    # 16, the first size measured from which the device call is never slower (0.065 against 0.095 ms at 64; a
+    # six-variable answer is faster on the device from 1 row).
+    QUERY_TEXT_MIN = 16
+    # ... and answers whose text would be longer than this (a policy cap, not a measurement: the text is one
+    # host buffer and one str); answer.iter_text has no ceiling
+    QUERY_TEXT_MAX_BYTES = 2 << 30
 
     def __init__(self, device: int = 0, stream=None, tuple_targets: bool = False,
                  stale_pattern_keys: bool = False):
@@ -210,6 +219,7 @@ class HipDB(RelationalDB):
         self.name_term_stats = {"device": 0, "host": 0}     # NameMatch terms evaluated by each path
         # answer.value_counts: calls answered by each path; tables counted without writing their rows / settled
         self.group_stats = {"device": 0, "host": 0, "unwritten": 0, "settled": 0}
+        self.query_text_stats = {"device": 0, "host": 0}    # answer.text / iter_text: calls answered by each path
         self._type_json = None          # das_atoms_json's type texts, per load
         self._template_cache = {}       # composite-type id -> template of its links, per load
 

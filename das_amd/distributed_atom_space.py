@@ -354,7 +354,7 @@ class DistributedAtomSpace:
             if query_answer.negation:
                 tag_not = "NOT "
             if output_format == QueryOutputFormat.HANDLE:
-                mapping = _format_assignments(query_answer.assignments)
+                mapping = query_answer.text(db=self.db)
             elif output_format in (QueryOutputFormat.ATOM_INFO, QueryOutputFormat.JSON):
                 # the reference calls .items() on a set here and raises
                 # (distributed_atom_space.py:312-318); kept as-is.

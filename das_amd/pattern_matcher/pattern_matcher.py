@@ -855,6 +855,155 @@ class PatternMatchingAnswer:
         sorted by handle on the host path)."""
         return list(self.value_counts(variable, db=db).handles)
 
+    def _text_plan(self, db, max_bytes):
+        """The device path's (table, literals) list, or None where text()
+        takes the host path (the rules are rows_text_plan's)."""
+        if (self._rel is None or self._py is not None or db is None or db is not self._db
+                or not isinstance(db, HipDB) or os.environ.get("DAS_QUERY_TEXT", "1") == "0"):
+            return None
+        return rows_text_plan(db.rel_local_tables(self._rel), db.QUERY_TEXT_MIN, max_bytes)
+
+    def text(self, db=None) -> str:
+        """str(self.assignments), the string DistributedAtomSpace.query
+        returns: "{" + ", ".join(repr(a.mapping) ...) + "}", or "set()" for
+        an empty answer.  The order of the rows is unspecified (set order on
+        the host path; table row order, table after table, on the device
+        path); each row is byte for byte the same on both.
+
+        Device path -- the answer still holds its device relation and no
+        Assignment objects, the DB is a HipDB, DAS_QUERY_TEXT is not "0",
+        every non-empty local table is ordered with at least one column, no
+        two tables bind the same set of variables (so no row repeats across
+        tables), and the answer has at least HipDB.QUERY_TEXT_MIN rows and at
+        most HipDB.QUERY_TEXT_MAX_BYTES bytes of text: one
+        das_table_rows_text call per table writes the rows' text where the
+        string is assembled -- no fetch, no handle string, no Assignment
+        object; a deferred product or scan view is not written.  Everything
+        else (empty answers, unordered or composite tables, hand-set
+        assignments, a sharded DB, a row beyond ROWS_TEXT_MAX_ROW, a value
+        that is no atom) formats the set as before.  `db.query_text_stats`
+        counts the calls of each path."""
+        db = db if db is not None else self._db
+        plan = self._text_plan(db, db.QUERY_TEXT_MAX_BYTES if isinstance(db, HipDB) else None)
+        if plan is not None:
+            out = _rows_text_device(db, plan)
+            if out is not None:
+                db.query_text_stats["device"] += 1
+                return out
+        if hasattr(db, "query_text_stats"):
+            db.query_text_stats["host"] += 1
+        from ..distributed_atom_space import _format_assignments
+        return _format_assignments(self.assignments)
+
+    def iter_text(self, chunk_rows=1 << 20, db=None):
+        """text() in pieces: a generator of str whose concatenation is
+        text(), for an answer too large to hold as one string (write each
+        piece to a socket or file).  On the device path one
+        das_table_rows_text call renders each chunk of `chunk_rows` rows;
+        braces and the ", " between chunks and tables are added here; a
+        deferred product is never written; there is no byte ceiling.  An
+        answer the device path does not take is one piece, the host text.  A
+        value that is no atom raises ValueError at its chunk."""
+        chunk_rows = int(chunk_rows)
+        if chunk_rows < 1:
+            raise ValueError("iter_text: chunk_rows must be positive")
+        db = db if db is not None else self._db
+        plan = self._text_plan(db, None)
+        if plan is None:
+            yield self.text(db=db)
+            return
+        db.query_text_stats["device"] += 1
+        yield from iter_rows_text(plan, chunk_rows, lambda t, lits, row0, n: _rows_text_chunk(db, t, lits, row0, n))
+
+
+ROW_SEP = b", "                      # between the rows of str(set)
+
+
+def row_literals(names):
+    """The literal pieces of repr({name: handle, ...}) around the handles, as
+    UTF-8 bytes: len(names) + 1 of them.  repr(name) is taken here, so a name
+    holding ' switches to double quotes, a backslash is doubled and a
+    printable non-ASCII letter stays as it is; a handle is 32 hex characters,
+    whose repr is the handle between single quotes."""
+    names = list(names)
+    if not names:
+        raise ValueError("row_literals: no variable")
+    lits = ["{" + repr(names[0]) + ": '"]
+    lits += ["', " + repr(n) + ": '" for n in names[1:]]
+    lits.append("'}")
+    return [s.encode("utf-8") for s in lits]
+
+
+def rows_text_plan(tables, min_rows=0, max_bytes=None):
+    """[(table, its row literals)] over the non-empty tables where
+    das_table_rows_text can render the answer, else None: every non-empty
+    table ordered with at least one column, the tables' variable sets
+    pairwise distinct, at least `min_rows` rows (and one), no row with its
+    separator beyond ROWS_TEXT_MAX_ROW bytes, and -- max_bytes not None -- a
+    text of at most that many bytes."""
+    tables = [t for t in tables if t.nrows]
+    if not tables or sum(t.nrows for t in tables) < min_rows:
+        return None
+    if any(t.kind != _lib.TABLE_ORDERED or len(t.vars) < 1 for t in tables):
+        return None
+    if len({frozenset(t.vars) for t in tables}) != len(tables):
+        return None
+    plan = [(t, row_literals(_var_name(v) for v in t.vars)) for t in tables]
+    if any(_lib.rows_text_size(lits, ROW_SEP, 1) + len(ROW_SEP) > _lib.ROWS_TEXT_MAX_ROW for _, lits in plan):
+        return None
+    if max_bytes is not None and rows_text_bytes(plan) > max_bytes:
+        return None
+    return plan
+
+
+def rows_text_bytes(plan):
+    """Bytes of the text of a rows_text_plan: the braces, every table's rows
+    and the separators between the tables."""
+    return 2 + sum(_lib.rows_text_size(lits, ROW_SEP, t.nrows) for t, lits in plan) + len(ROW_SEP) * (len(plan) - 1)
+
+
+def iter_rows_text(plan, chunk_rows, render):
+    """The pieces of a plan's text: "{", render(table, literals, row0, n) for
+    every chunk of at most chunk_rows rows, table after table, each but the
+    first led by ", ", and "}"."""
+    yield "{"
+    sep = ""
+    for t, lits in plan:
+        for row0 in range(0, t.nrows, chunk_rows):
+            yield sep + render(t, lits, row0, min(chunk_rows, t.nrows - row0))
+            sep = ROW_SEP.decode()
+    yield "}"
+
+
+def _rows_text_chunk(db, t, lits, row0, n):
+    res = db.ctx.rows_text(t, lits, ROW_SEP, row0=row0, nrows=n)
+    if res is None:
+        raise ValueError("iter_text: a row beyond ROWS_TEXT_MAX_ROW bytes")
+    data, total, bad = res
+    if bad or total != data.size:
+        raise ValueError(f"iter_text: {bad} values of rows {row0}..{row0 + n} are no atoms")
+    return str(memoryview(data), "utf-8")
+
+
+def _rows_text_device(db, plan):
+    """text() over a rows_text_plan: every table's rows written by one
+    das_table_rows_text call into its place in one buffer, decoded once.
+    None where a call refuses a row or meets a value that is no atom."""
+    buf = np.empty(rows_text_bytes(plan), dtype=np.uint8)
+    buf[0] = ord("{")
+    at = 1
+    for i, (t, lits) in enumerate(plan):
+        if i:
+            buf[at:at + len(ROW_SEP)] = np.frombuffer(ROW_SEP, dtype=np.uint8)
+            at += len(ROW_SEP)
+        size = _lib.rows_text_size(lits, ROW_SEP, t.nrows)
+        res = db.ctx.rows_text(t, lits, ROW_SEP, out=buf[at:at + size])
+        if res is None or res[1] != size or res[2]:
+            return None
+        at += size
+    buf[at] = ord("}")
+    return str(memoryview(buf), "utf-8")
+
 
 def value_counts_host(db, answer, variable):
     """The definition of PatternMatchingAnswer.value_counts, over any

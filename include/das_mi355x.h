@@ -295,6 +295,34 @@ int das_group_counts(das_ctx_t* ctx, const das_table_t* const* ts, const int32_t
                      uint32_t* out_ids, uint64_t* out_counts, uint64_t cap, uint64_t* n_groups,
                      uint64_t stats[2] /* tables counted unwritten, tables settled */);
 
+/* ---- ordered rows as text (str(answer.assignments), one device call) ------- */
+#define DAS_ROWS_TEXT_STAGE_BYTES 16384 /* bytes of one tile's image of the output in LDS */
+/* a row's text and its separator at most: one row and the tile's alignment slack fit the stage */
+#define DAS_ROWS_TEXT_MAX_ROW (DAS_ROWS_TEXT_STAGE_BYTES - 16)
+/* Rows [row0, row0 + nrows) of an ORDERED table as text.  The text of row r is
+ * lit[0] hex(col0[r]) lit[1] hex(col1[r]) .. lit[ncols]: `lit` holds the
+ * ncols + 1 literal pieces back to back, piece i at lit_off[i] .. lit_off[i + 1]
+ * (ncols + 2 ascending offsets); hex(id) is the 32 lower-case hex characters of
+ * the atom's 16 digest bytes in memory order (its handle).  The rows are joined
+ * by the sep_len bytes of `sep`, with no separator after the last.  The call
+ * fills holes between the caller's literals and knows no format.
+ * Every row has R = the literals' bytes + 32 * ncols bytes, so *n_bytes =
+ * nrows * R + (nrows - 1) * sep_len (0 for no rows) whatever `cap` is;
+ * min(total, cap) bytes are copied to `out` and nothing is stored at or past
+ * out[cap] (as das_node_names).  *n_bad = the cells whose id is >= n_atoms; if
+ * it is non-zero the text is unspecified.
+ * DAS_ERR_INVALID: the table is not ORDERED or has no column, the rows are out
+ * of range, or lit_off is not ascending.  DAS_ERR_LIMIT: R + sep_len exceeds
+ * DAS_ROWS_TEXT_MAX_ROW.
+ * Unresolved answers (see das_table_fetch): a scan view is read in place and a
+ * deferred product from its factors -- neither is written, both stay
+ * unresolved; a deferred index join is settled first.  An answer that reads
+ * index arrays is read only through the context that made it.  One launch and
+ * one wait per call. */
+int das_table_rows_text(das_ctx_t* ctx, const das_table_t* t, uint64_t row0, uint64_t nrows, const uint8_t* lit,
+                        const uint32_t* lit_off /* ncols + 2 */, const uint8_t* sep, uint32_t sep_len,
+                        uint8_t* out, uint64_t cap, uint64_t* n_bytes, uint64_t* n_bad);
+
 /* ---- atom documents in bulk (redis_mongo_db.py:187-199, 297-314) ---------- */
 #define DAS_DOC_MAX_DEPTH 16 /* levels of a deep representation (a root is level 1) */
 /* json.dumps(deep representation, sort_keys=False, indent=4) of n atoms as
